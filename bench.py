@@ -15,11 +15,15 @@ hot path, inputs resident in HBM:
   fp64) runs on a second HIP stream concurrently with the encode + dense search.
 
 value = queries/s of the whole job (each query searches all N x shard chunks).
-The CPU baseline is the oracle (oracle/) run on this host on a bounded sample
-of the same queries over the same shard; recall@10 compares the GPU's final
-top-10 with the oracle's.
 
-  python bench.py [--gpus N --steps K --warmup W] [--mode hybrid|dense|ingest]
+A plain run sets up, warms up, times --steps steps and prints the result line.
+--full adds everything else: the rooflines, the other E5 precision, the dense,
+ingest and near-duplicate legs, and the CPU baseline -- the oracle (oracle/) run
+on this host on a bounded sample of the same queries over the same shard;
+recall@10 compares the GPU's final top-10 with the oracle's.  --dump-outputs DIR
+writes the last timed step's results as DIR/<name>.npy.
+
+  python bench.py [--gpus N --steps K --warmup W] [--mode hybrid|dense|ingest|e2e] [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -122,12 +126,62 @@ def parse_args():
     ap.add_argument("--cpu-queries", type=int, default=128)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps also run everything else the benchmark measures or checks: "
+                         "the rooflines, the other E5 precision, the dense / ingest / near-duplicate legs, the CPU "
+                         "baseline with recall@10 (hybrid mode; each still has its own switch above) and e2e mode's "
+                         "latency and construct-then-retrieve legs.  Without it: set up, warm up, time --steps steps, "
+                         "print the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32 / float64; same arguments -> same inputs, so two builds can be "
+                         "compared array for array)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def log(*a):
     if int(os.environ.get("RANK", "0")) == 0:
         print("[bench]", *a, file=sys.stderr, flush=True)
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: {name: array} -> DIR/<name>.npy, float32 kept, everything else as float64
+    (int64 keys are row numbers < 2^53: exact).  At most 64 MB in all: an array over its share is
+    cut to a fixed (seeded) sorted sample of its rows, the same rows in every run."""
+    import numpy as np
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    share = DUMP_CAP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes > share:
+            a = a.reshape(a.shape[0], -1) if a.ndim > 1 else a.reshape(-1, 1)
+            keep = max(1, share // (a.shape[1] * a.itemsize))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(d / f"{name}.npy", a)
+    log(f"outputs of the last timed step written to {d}: {', '.join(arrays)}")
+
+
+def fused_arrays(res):
+    """rrf_merge_dev's result tuple as host arrays with everything the caller must not read
+    blanked: slots past a query's count (key -1, scores 0), and the distance / BM25 score of items
+    the list does not hold (flags bit 0 / bit 1)."""
+    import numpy as np
+    keys, fused, vdist, bscore, flags, n = (t.cpu().numpy() for t in res)
+    nb = min(keys.shape[0], n.shape[0])          # N > 1: keys are all-gathered, the rest is this rank's block
+    live = np.arange(fused.shape[1])[None, :] < n[:, None]
+    keys = keys.copy()
+    keys[:nb][~live[:nb]] = -1
+    flags = np.where(live, flags, 0)
+    return {"fused_keys": keys, "fused_score": np.where(live, fused, 0.0),
+            "vector_distance": np.where(flags & 1, vdist, np.float32(0)).astype(np.float32),
+            "bm25_score": np.where(flags & 2, bscore, 0.0), "flags": flags, "count": n}
 
 
 # ---------------------------------------------------------------------------
@@ -152,9 +206,12 @@ def gen_tokens(n, vocab, s, avg_len, seed, chunk=1 << 27):
     doc_off = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
     torch.cumsum(lens, 0, out=doc_off[1:])
     ntok = int(doc_off[-1].item())
-    p = 1.0 / torch.arange(1, vocab + 1, dtype=torch.float64, device="cuda").pow(s)
-    cdf = torch.cumsum(p, 0)
-    cdf /= cdf[-1].clone()
+    # the Zipf cdf is summed on the host: a device cumsum of floats combines its blocks' partial sums
+    # in the order they finish, so its last bits -- and with them a few of the 1.2e9 drawn tokens, the
+    # terms' df and every BM25 score's last digits -- changed from run to run
+    import numpy as np
+    cdf = np.cumsum(1.0 / np.arange(1, vocab + 1, dtype=np.float64) ** s)
+    cdf = torch.from_numpy(cdf / cdf[-1]).to("cuda")
     tokens = torch.empty(ntok, dtype=torch.int32, device="cuda")
     for t0 in range(0, ntok, chunk):
         m = min(chunk, ntok - t0)
@@ -230,7 +287,7 @@ def main():
             torch.distributed.broadcast(qt, src=0)
         q_terms = qt.reshape(-1).contiguous()
         q_off = (torch.arange(B + 1, device=dev, dtype=torch.int32) * args.q_terms).contiguous()
-        if args.cpu_baseline:    # the recall leg's oracle builds its own CSR from these
+        if args.full and args.cpu_baseline:    # the recall leg's oracle builds its own CSR from these
             tokens_host = (tokens.cpu().numpy(), doc_off.cpu().numpy())
         del tokens, doc_off
         torch.cuda.empty_cache()
@@ -454,6 +511,12 @@ def main():
     if bm25 is not None:
         bm25.timing(True)
     elapsed, res = timed(args.steps)
+    if args.dump_outputs and rank == 0:      # before the side legs reuse the step's buffers
+        if args.mode == "dense":
+            d_h, r_h = dout[0].cpu().numpy(), dout[1].cpu().numpy()
+            dump_outputs(args.dump_outputs, {"dense_rows": r_h, "dense_distance": np.where(r_h >= 0, d_h, np.float32(0))})
+        else:
+            dump_outputs(args.dump_outputs, fused_arrays(res))
     # the recall check compares `res` with the oracle on the SAME step's inputs: keep this run's
     # query embeddings and merged lists before the side legs reuse the buffers (qfull at N > 1)
     q_main = ((qfull if ws > 1 else last_lists.get("q", e5["qbuf"])) if use_e5 else qfix).clone()
@@ -487,9 +550,12 @@ def main():
         + (f", bm25 search {bsearch_ms:.3f} ms{' after the encode' if gated_run else ''} (K2a tail pass {bm25_ms:.3f} ms, {rescored} (query, range) pairs "
            f"re-scored)" if bm25_ms is not None else ""))
 
-    roofs = {"dense": _dense_roofline(kind, N, D, B, dense_ms,
-                                      _pmc_traffic(args, {5: "dense_q8", 6: "dense_q8s"}.get(kind, "dense")))}
-    if bm25 is not None:
+    # everything from here to the result line is --full's: rooflines, side legs, CPU baseline + recall
+    roofs = {}
+    if args.full:
+        roofs["dense"] = _dense_roofline(kind, N, D, B, dense_ms,
+                                         _pmc_traffic(args, {5: "dense_q8", 6: "dense_q8s"}.get(kind, "dense")))
+    if args.full and bm25 is not None:
         roofs["bm25"] = _bm25_roofline(bm25, q_terms, N, bm25_ms, _pmc_traffic(args, "bm25"), args.q_terms)
         if bm25b_ms is not None:
             roofs["bm25_block"] = _bm25_block_roofline(bm25, q_terms, bm25.workspace_items(B, q_terms.numel(), K, bws),
@@ -498,14 +564,14 @@ def main():
     # the headline roofline: the kernel with the most algorithmic work per step (K1q: 7.76 GB per launch
     # against K2a's 0.25 GB).  In-step launch times are not a fair ranking: the two run side by side and
     # whichever starts second is stretched by the other (rooflines.bm25 keeps K2a's line either way)
-    dominant = max(roofs, key=lambda n: roofs[n].get("algorithmic_per_launch", {}).get("bytes", 0.0))
-    roof = roofs[dominant]
-    if use_e5:   # the whole encode (48 K10 GEMMs + attention + LayerNorms) against the MFMA peak
+    dominant = max(roofs, key=lambda n: roofs[n].get("algorithmic_per_launch", {}).get("bytes", 0.0), default=None)
+    roof = roofs[dominant] if roofs else None
+    if args.full and use_e5:   # the whole encode (48 K10 GEMMs + attention + LayerNorms) against the MFMA peak
         roofs["e5"] = _e5_roofline(bq, args.q_tokens, args.e5_layers, e5_ms, args.e5_dtype)
 
     # side legs (not the headline): the other E5 precision, and the north_star dense configs
     legs = {}
-    if use_e5 and args.e5_other_leg:
+    if args.full and use_e5 and args.e5_other_leg:
         other = "bfloat16" if args.e5_dtype == "float32" else "float32"
         main_e5, e5 = e5, make_e5(other)
         pipe_stream, pipe["stream"] = pipe["stream"], None     # the other precision's leg runs unpipelined
@@ -518,14 +584,14 @@ def main():
         log(f"{other} E5 leg: {B * args.steps / el2:.1f} q/s ({el2 / args.steps * 1e3:.3f} ms/step)")
         del e5
         e5 = main_e5
-    if args.mode == "hybrid" and args.dense_legs:
+    if args.full and args.mode == "hybrid" and args.dense_legs:
         legs.update(dense_legs(args, dense, N, D, dev, ws, q_main, P))
         # the in-step launch shares its CUs with the BM25 stream (launched after the encode, beside
         # the dense search, since round 4), so its HIP-event time includes that time-sharing; the
         # same launch alone (the step's own queries, same shard) is the kernel's own roofline
         if "c4_dense_10m_b256" in legs:
             roof["standalone"] = legs["c4_dense_10m_b256"]["roofline"]
-    if use_e5 and args.ingest_leg:
+    if args.full and use_e5 and args.ingest_leg:
         e5_f32 = e5["emb"] if e5["dtype"] == "float32" else None
         legs["ingest_fp32"], roofs["e5_ingest"] = ingest_leg(args, e5_f32, dev, ws, rank)
         if args.varlen_chunks > 0:
@@ -537,7 +603,7 @@ def main():
         "metric": METRIC if args.mode == "hybrid" else f"dense cosine top-{K} queries/sec, {N}x{D} fp32",
         "value": qps, "unit": "queries/s", "n_gpus": ws, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None,
+        "vs_baseline": None, "full": args.full,
         "dtype": (("fp32-accurate E5 (K10 f16x3 MFMA) + " + ("int8/f16/f64" if kind in (5, 6) else "f16/f64")
                    + " dense + f64 BM25") if use_e5 and args.e5_dtype == "float32" else "f16+f64"),
         "dtypes": {"dense_knn": {1: "f32 (MFMA)", 3: "f16 coarse (MFMA) + fp64 exact re-rank of the certified band",
@@ -565,11 +631,11 @@ def main():
         "dense_exact_reruns": fallbacks,
         "bm25_rescored_pairs": rescored,
         "roofline": roof,
-        "rooflines": roofs,
+        "rooflines": roofs or None,
         **legs,
         "env": {e: os.environ[e] for e in KNOB_ENV if e in os.environ},
     }
-    if args.cpu_baseline and args.mode == "hybrid":
+    if args.full and args.cpu_baseline and args.mode == "hybrid":
         cpu, recall = cpu_baseline_and_recall(args, dense, bm25, res, q_terms, q_main, rank, ws, row0, N,
                                               lists_main, tokens_host)
         tokens_host = None
@@ -578,7 +644,7 @@ def main():
     else:
         out["cpu_baseline"] = None
         out["recall_at_10"] = None
-    if args.mode == "hybrid" and args.dense_legs and ws == 1:
+    if args.full and args.mode == "hybrid" and args.dense_legs and ws == 1:
         # last: it plants rows into the shard (after the recall check has read it)
         out["c4_dup_cluster_b256"] = dup_cluster_leg(args, dense, N, D, dev, q_main, P,
                                                      legs.get("c4_dense_10m_b256", {}).get("ms_per_step"))
@@ -1331,10 +1397,18 @@ def run_e2e(args, rank, ws, dev):
             log(f"retrieve() {name}: p50 {lat_all[name]['p50']:.2f} ms, p99 {lat_all[name]['p99']:.2f} ms ({paths[name]})")
         return lat_all, paths
 
-    lat, paths = latencies()
-    construct = construct_leg(args, vs, bm, embedder, qs, K, dev, none_keys, lat) if args.e2e_construct else None
+    if args.dump_outputs:            # the last timed call's result dicts as arrays (ids are "c<row>")
+        rows = np.full((B, K), -1, np.int64)
+        fused = np.zeros((B, K))
+        for i, rs in enumerate(res):
+            for j, r in enumerate(rs[:K]):
+                rows[i, j], fused[i, j] = int(r["id"][1:]), r["scores"]["fused"]
+        dump_outputs(args.dump_outputs, {"result_rows": rows, "fused_score": fused})
+    # --full: single-query latencies and ask_question's construct-then-retrieve sequence
+    lat, paths = latencies() if args.full else ({}, {})
+    construct = construct_leg(args, vs, bm, embedder, qs, K, dev, none_keys, lat) if args.full and args.e2e_construct else None
     lat_same = None
-    if args.e2e_ab_same_stream:       # A/B: BM25 on the main stream behind the dense search (the old schedule)
+    if args.full and args.e2e_ab_same_stream:     # A/B: BM25 on the main stream behind the dense search (the old schedule)
         os.environ["CLASSMATE_BM25_SAME_STREAM"] = "1"
         try:
             log("A/B: BM25 on the main stream")
@@ -1347,16 +1421,16 @@ def run_e2e(args, rank, ws, dev):
         "metric": f"drop-in HybridRetriever.retrieve_batch queries/sec (strings -> result dicts), {N} chunks",
         "value": qps, "unit": "queries/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "fp32 E5 + int8/f16/f64 dense + f64 BM25",
+        "vs_baseline": None, "full": args.full, "dtype": "fp32 E5 + int8/f16/f64 dense + f64 BM25",
         "data": "synthetic (seeded): Zipf-word chunks, random unit embeddings, random-init E5-base weights",
         "config": {"workload": "drop-in retrieve_batch (E5 query encode + cosine pool 24 + MMR 8 + BM25 8 + RRF)",
                    "chunks": N, "words_per_chunk": args.e2e_words, "global_batch": B, "top_k": K, "dim": D},
-        "retrieve_latency_ms": lat["unfiltered"],
-        "retrieve_latency_ms_by_filter": lat,
+        "retrieve_latency_ms": lat.get("unfiltered"),
+        "retrieve_latency_ms_by_filter": lat or None,
         "retrieve_latency_ms_bm25_same_stream": lat_same,
         "retrieve_batch_env_ab_qps": ab_env or None,
         "construct_then_retrieve": construct,
-        "retrieve_paths": paths,
+        "retrieve_paths": paths or None,
         "results_returned": n_res, "setup_s": time.perf_counter() - t_setup,
         "retrieve_batch_path": ("device-resident (retrieval/device_batch.py)"
                                 if os.environ.get("CM_RETRIEVE_DEVICE", "1") != "0" and device_batch.applicable(retr, {}, True)
@@ -1561,12 +1635,14 @@ def run_ingest(args, rank, ws, dev):
     if ws > 1:
         torch.distributed.barrier()
     el = parallel.max_over_ranks(time.perf_counter() - t0, device=dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"embeddings": out.cpu().numpy()})
     flops_seq = args.e5_layers * (24 * S * 768 ** 2 + 4 * S * S * 768)
     val = B * ws * args.steps / el
     res = {"metric": "E5-base ingest encode chunks/sec (forward + HIP mean-pool/L2)", "value": val,
            "unit": "chunks/s", "n_gpus": ws, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": el / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-           "dtype": {"bfloat16": "bf16", "float32": "fp32"}[args.e5_dtype],
+           "full": args.full, "dtype": {"bfloat16": "bf16", "float32": "fp32"}[args.e5_dtype],
            "data": "synthetic token ids, random-init E5-base weights",
            "config": {"workload": "E5-base encode", "global_batch": B * ws, "seq_len": S,
                       "parallelism": f"replicas x{ws}"},
