@@ -62,6 +62,8 @@ SIGNATURES = {
     "cm_dense_upsert": (c_int, c_vp, c_vp, c_vp, c_i64),
     "cm_dense_upsert_dev": (c_int, c_vp, c_vp, c_i64, c_i64, c_vp),
     "cm_dense_delete": (c_int, c_vp, c_vp, c_i64),
+    "cm_dense_compact": (c_int, c_vp, c_i64, c_i32, c_vp, c_vp),
+    "cm_dense_truncate": (c_int, c_vp, c_i64),
     "cm_dense_reset": (c_int, c_vp),
     "cm_dense_live_count": (c_i64, c_vp),
     "cm_dense_size": (c_i64, c_vp),

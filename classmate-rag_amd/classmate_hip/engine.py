@@ -133,6 +133,31 @@ class DenseIndex:
     def reset(self):
         L.check(L.fn["cm_dense_reset"](self._h), "cm_dense_reset")
 
+    def compact(self, expect_live: Optional[int] = None, shrink: bool = False) -> np.ndarray:
+        """Move the live rows to [0, n) in ascending order and drop the rest (cm_dense_compact);
+        returns the old row of every new row (int64, length n = the new size).  ``expect_live``
+        that differs from the device's live count raises ValueError before anything is written;
+        ``shrink`` also gives the freed device memory back."""
+        n = self.live_count() if expect_live is None else int(expect_live)
+        if n < 0:
+            raise ValueError("expect_live must be >= 0")
+        old = np.empty(max(n, 1), np.int64)
+        new_size = C.c_int64(-1)
+        L.check(L.fn["cm_dense_compact"](self._h, n, int(bool(shrink)), L.ptr(old), C.byref(new_size)),
+                "cm_dense_compact")
+        return old[:new_size.value]
+
+    def truncate(self, new_size: int):
+        """Drop rows >= new_size (cleared as in a never-written store) -- cm_dense_truncate."""
+        L.check(L.fn["cm_dense_truncate"](self._h, int(new_size)), "cm_dense_truncate")
+
+    def live_mask(self) -> np.ndarray:
+        """Host bool mask of rows [0, size): the live bits alone (no row data is copied)."""
+        n = self.size
+        live = np.zeros(max((n + 31) // 32, 1), np.uint32)
+        L.check(L.fn["cm_dense_export"](self._h, 0, n, None, L.ptr(live)), "cm_dense_export")
+        return np.unpackbits(live.view(np.uint8), bitorder="little")[:n].astype(bool)
+
     # -- queries ---------------------------------------------------------
     @property
     def size(self) -> int:

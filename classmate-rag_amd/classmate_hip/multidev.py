@@ -195,6 +195,55 @@ class ShardedDenseIndex(_Shards):
         for s, sh in enumerate(self.shards):
             sh.reserve(self.map.local_count(s, capacity))
 
+    _COMPACT_STAGE_BYTES = 64 << 20   # rows gathered onto the first device per step of compact()
+
+    def compact(self, expect_live: Optional[int] = None, shrink: bool = False) -> np.ndarray:
+        """DenseIndex.compact over the shards: the live global rows move to [0, n) in ascending
+        order -- which moves rows between shards, since global rows are dealt in blocks -- and the
+        old global row of every new row is returned.
+
+        The global map old_of_new comes from the shards' live bits (host).  Then, for every
+        destination piece of new rows in ascending order (a piece never crosses a block, so it is
+        one contiguous local range of one shard), the source rows are gathered onto the first
+        device and upserted into the owner's range.  In place is safe as in cm_dense_compact, on
+        global rows: old_of_new is increasing, so a piece [d0, d0 + m) reads old rows >= d0 only
+        and the pieces after it read old rows >= d0 + m; local slot <-> global row is a bijection,
+        so the slots a piece overwrites hold rows that were already moved, were dead, or belong to
+        the piece itself and were gathered before its upsert.  Every shard is then truncated to
+        its share of [0, n)."""
+        live = np.zeros(self.size, bool)
+        for s, sh in enumerate(self.shards):
+            ns = sh.size
+            if ns:
+                live[self.map.to_global(s, np.arange(ns, dtype=np.int64))] = sh.live_mask()
+        old_of_new = np.nonzero(live)[0].astype(np.int64)
+        n = int(old_of_new.shape[0])
+        if expect_live is not None and int(expect_live) != n:
+            raise ValueError(f"compact: the shards hold {n} live rows, the caller expected {int(expect_live)}")
+        if n < live.shape[0]:
+            moved = np.nonzero(old_of_new != np.arange(n))[0]
+            step = max(1, self._COMPACT_STAGE_BYTES // (self.dim * 4))
+            dev0 = torch.device("cuda", self.device)
+            d0 = int(moved[0]) if moved.size else n
+            while d0 < n:
+                m = min(step, n - d0, self.map.B - (d0 & (self.map.B - 1)))
+                s, l = self.map.owner_local(np.array([d0], np.int64))
+                s, l = int(s[0]), int(l[0])
+                with torch.cuda.device(dev0):
+                    vecs = self.gather_dev(torch.from_numpy(old_of_new[d0:d0 + m]).to(dev0))
+                    torch.cuda.synchronize(dev0)          # gathered before the owner is written
+                dev_s = torch.device("cuda", self.devices[s])
+                with torch.cuda.device(dev_s):
+                    self.shards[s].upsert_dev(vecs.to(dev_s).contiguous(), l)
+                    torch.cuda.synchronize(dev_s)         # written before the next piece reads
+                d0 += m
+            for s, sh in enumerate(self.shards):
+                sh.truncate(min(sh.size, self.map.local_count(s, n)))
+        if shrink:
+            for s, sh in enumerate(self.shards):
+                sh.compact(shrink=True)
+        return old_of_new
+
     def mem_stats(self) -> dict:
         st = [sh.mem_stats() for sh in self.shards]
         return {"bytes": sum(x["bytes"] for x in st), "peak_bytes": sum(x["peak_bytes"] for x in st),

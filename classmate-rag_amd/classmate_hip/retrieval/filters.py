@@ -236,6 +236,39 @@ class MetaIndex:
             m.tags[t] = set(rows[off[j]: off[j + 1]].tolist())
         return m
 
+    def compacted(self, keep) -> "MetaIndex":
+        """The index of rows ``keep`` (ascending old rows) renumbered 0..len(keep)-1, after the
+        stores' compact(): a new object (fresh uid: device caches keyed on it miss) that evaluates
+        every where clause as a MetaIndex filled by ``set()`` with the surviving metadata in order
+        would.  The value -> code maps and n_odd (removed rows already left it) carry over; codes
+        of values no surviving row holds simply match no row."""
+        keep = np.asarray(keep, np.int64)
+        n_old, n = len(self.metas), int(keep.shape[0])
+        if n and (np.any(np.diff(keep) <= 0) or keep[0] < 0):
+            raise ValueError("keep must be ascending row numbers")
+        m = MetaIndex()
+        inside = keep < n_old                     # rows past the metadata were never given any
+        src = np.where(inside, keep, 0)
+        cap = max(n, 1024)
+        m._cap = cap
+        m.metas = [self.metas[int(r)] if r < n_old else None for r in keep]
+        m.live = np.zeros(cap, bool)
+        if n and n_old:
+            m.live[:n] = self.live[src] & inside
+        for key, c in self.cols.items():
+            col = _Column(cap)
+            if n and n_old:
+                col.py[:n] = np.where(inside, c.py[src], _MISSING)
+                col.ty[:n] = np.where(inside, c.ty[src], _MISSING)
+            col.py_map, col.ty_map, col.n_odd = dict(c.py_map), dict(c.ty_map), c.n_odd
+            m.cols[key] = col
+        for t, rs in self.tags.items():
+            old = np.fromiter(rs, np.int64, count=len(rs))
+            pos = np.searchsorted(keep, old)
+            hit = (pos < n) & (keep[np.minimum(pos, max(n - 1, 0))] == old) if n else np.zeros(old.shape[0], bool)
+            m.tags[t] = set(pos[hit].tolist())
+        return m
+
     def remove(self, row: int):
         if row >= len(self.metas) or not self.live[row]:
             return

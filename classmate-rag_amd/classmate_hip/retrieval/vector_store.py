@@ -567,6 +567,46 @@ class GpuVectorStore:
             return 0
 
     @_locked
+    def compact(self, shrink: bool = False) -> Dict[str, int]:
+        """Give deleted rows back: the hook ``vacuum_indexes`` probes for (rag/admin/backup.py:178-202,
+        ``if hasattr(vec_store, "compact")``).  The surviving rows keep their order and are
+        renumbered 0..n-1 on the device and in every host table (so they line up with the BM25
+        store's again); with a directory and ``autosave`` the files are rewritten without the
+        holes.  ``shrink`` also returns the freed device memory.  A collection without dead rows
+        is left as it is (no version bump, no write)."""
+        self._ensure_loaded()
+        before = len(self._ids)
+        if self._index is None:
+            return {"rows_before": before, "rows_after": before, "bytes_before": 0, "bytes_after": 0}
+        bytes_before = int(self._index.mem_stats()["bytes"])
+        if before == len(self._row):
+            if shrink:
+                self._index.compact(expect_live=before, shrink=True)
+            return {"rows_before": before, "rows_after": before, "bytes_before": bytes_before,
+                    "bytes_after": int(self._index.mem_stats()["bytes"])}
+        keep = [r for r, i in enumerate(self._ids) if i is not None]
+        # documents and metadata of a cold-opened collection are parsed through line_off: read the
+        # survivors' before the offsets go
+        docs = [self._docs[r] for r in keep]
+        meta = self._meta.compacted(keep)
+        got = self._index.compact(expect_live=len(keep), shrink=shrink)
+        if got.shape[0] != len(keep) or not np.array_equal(got, np.asarray(keep, np.int64)):
+            raise RuntimeError("compact: the device's live rows differ from the host's id table")
+        self._ids = [self._ids[r] for r in keep]
+        self._docs = docs
+        self._row = {i: r for r, i in enumerate(self._ids)}
+        self._meta = meta
+        self._st.line_off = None
+        self._st.tail = 0
+        self._version += 1
+        if self._dir is not None and self.autosave:
+            self.save()
+        else:
+            self._changed(False)
+        return {"rows_before": before, "rows_after": len(self._ids), "bytes_before": bytes_before,
+                "bytes_after": int(self._index.mem_stats()["bytes"])}
+
+    @_locked
     def reset_collection(self) -> None:
         self._ensure_loaded()
         if self._index is not None:

@@ -1563,20 +1563,13 @@ void dense_free_rows(cm_dense *h) {
   dense_set_rows(h, RowArrays{});
 }
 
-int dense_grow(cm_dense *h, int64_t need_rows) {
-  if (need_rows <= h->rows_alloc) return CM_OK;
-  int64_t cap = std::max<int64_t>(need_rows, h->rows_alloc + h->rows_alloc / 2);
-  cap = round_up(std::max<int64_t>(cap, kStepRows), kStepRows);
+// Reallocate the row arrays at `cap` rows (a multiple of kStepRows that holds every written row),
+// through the host (staged) or device to device: the body of dense_grow, shared with the
+// compaction's shrink (cm_dense_compact.inc).
+int dense_realloc(cm_dense *h, int64_t cap, bool staged) {
   const int64_t keep = std::min<int64_t>(round_up(h->size, kStepRows), h->rows_alloc);  // rows holding data
   RowArrays a;
   int rc;
-  bool staged = keep > 0 && h->mem_cur > kStageBytes;
-  if (staged && h->grow_mode == 0) {   // auto: copy on the device when old + new fit with slack
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess &&
-        (int64_t)free_b >= dense_row_bytes(h, cap) + kGrowSlack)
-      staged = false;
-  }
   if (staged) {
     // host-staged: fp32 rows + norms + live bits out, old arrays freed, new ones in
     const size_t cb = (size_t)keep * h->ld * 4, ib = (size_t)keep * 4, lb = (size_t)keep / 8;
@@ -1663,6 +1656,21 @@ int dense_grow(cm_dense *h, int64_t need_rows) {
   h->rows_alloc = cap;
   h->mem_cur = dense_row_bytes(h, cap);
   return CM_OK;
+}
+
+int dense_grow(cm_dense *h, int64_t need_rows) {
+  if (need_rows <= h->rows_alloc) return CM_OK;
+  int64_t cap = std::max<int64_t>(need_rows, h->rows_alloc + h->rows_alloc / 2);
+  cap = round_up(std::max<int64_t>(cap, kStepRows), kStepRows);
+  const int64_t keep = std::min<int64_t>(round_up(h->size, kStepRows), h->rows_alloc);  // rows holding data
+  bool staged = keep > 0 && h->mem_cur > kStageBytes;
+  if (staged && h->grow_mode == 0) {   // auto: copy on the device when old + new fit with slack
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess &&
+        (int64_t)free_b >= dense_row_bytes(h, cap) + kGrowSlack)
+      staged = false;
+  }
+  return dense_realloc(h, cap, staged);
 }
 
 // Timing ablations are compiled only into -DCM_ABLATION builds (tools/build_variant.sh); the
@@ -2538,3 +2546,5 @@ int cm_dense_search(cm_dense *h, const float *q, int32_t nq, int32_t k, const ui
 
 }  // extern "C"
 
+// cm_dense_compact / cm_dense_truncate: reclaiming deleted rows
+#include "cm_dense_compact.inc"

@@ -87,6 +87,26 @@ int cm_dense_upsert(cm_dense *h, const float *vecs, const int64_t *rows, int64_t
 int cm_dense_upsert_dev(cm_dense *h, const float *vecs_dev, int64_t row0, int64_t n, void *stream);
 /* col.delete (vector_chroma.py:181-187): clear the live bit of rows. */
 int cm_dense_delete(cm_dense *h, const int64_t *rows, int64_t n);
+/* vec_store.compact(), the hook vacuum_indexes probes for (rag/admin/backup.py:178-202): give the
+ * rows that col.delete (rag/retrieval/vector_chroma.py:181-187) marked dead back.  The live rows of
+ * [0, size) move to [0, n) in ascending order (ties -> lower row and the insertion order survive),
+ * size becomes n, and everything at rows >= n is cleared as in a never-written store.
+ * old_rows_out (nullable; caller-owned host memory for expect_live entries, or for
+ * cm_dense_live_count entries when expect_live < 0) receives the old row of every new row;
+ * *new_size (nullable) receives n.  expect_live >= 0 that differs from the device's live count ->
+ * CM_EINVAL, a failed staging allocation -> CM_ENOMEM, both before anything is modified.  A store
+ * without dead rows is left untouched (the map is the identity).  shrink != 0: also reallocate
+ * the row arrays at round_up(max(n, 128), 128) rows when that is smaller (device to device when old
+ * and new fit in free memory, else through the host; a store that fits neither way keeps its arrays,
+ * which is not an error).  Host function: waits for the device's pending work, runs on the handle's
+ * stream and returns when done; no search or upsert may run concurrently.  Under cm_dense_timing
+ * a compaction that moves rows records three event pairs: rank, move, plane rebuild + tail. */
+int cm_dense_compact(cm_dense *h, int64_t expect_live, int32_t shrink, int64_t *old_rows_out, int64_t *new_size);
+/* Drop rows >= new_size: they are cleared as in a never-written store (fp32 rows, norms, both
+ * coarse planes, scales, live bits; the scale groups of the 64-row tile that new_size cuts are
+ * re-quantised) and size becomes new_size.  new_size > size (or < 0) -> CM_EINVAL.  The last step of
+ * cm_dense_compact, and of a sharded compaction on every shard.  No reference counterpart. */
+int cm_dense_truncate(cm_dense *h, int64_t new_size);
 /* ChromaVectorStore.reset_collection (vector_chroma.py:262-269). */
 int cm_dense_reset(cm_dense *h);
 /* ChromaVectorStore.count (vector_chroma.py:255-260). */
