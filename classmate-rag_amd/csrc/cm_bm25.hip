@@ -1391,6 +1391,10 @@ BmWs bm_ws_layout(const cm_bm25 *h, int nq, int total_terms, int k, void *base) 
 #ifndef K2B_GRID
 #define K2B_GRID 2048  // K2b workgroups (grid-stride over the planned items)
 #endif
+#if K2A_TRACE
+DevBuf g_k2a_trace_buf;          // diagnostic builds: the last K2a launch's per-unit records
+int64_t g_k2a_trace_units = 0;
+#endif
 // Launch K2 + merge given q_idf and *avgdl already in the workspace.
 int bm25_launch_core(cm_bm25 *h, const int32_t *q_terms_dev, const int32_t *q_off_dev, int nq, int total_terms, int k,
                      const uint32_t *allow_dev, const BmWs &w, double *score_dev, int64_t *row_dev, hipStream_t st,
@@ -1434,18 +1438,27 @@ int bm25_launch_core(cm_bm25 *h, const int32_t *q_terms_dev, const int32_t *q_of
   // K2a's own run length (a multiple of its super-range when possible): shorter runs -> more,
   // shorter waves (better balance of the Zipf-skewed work at the end of the grid)
   const int rpw_a = std::max(1, std::min(rpw, (int)K2A_RPW));
-  const int64_t nblk_a = ceil_div(nqg * ceil_div(nr, rpw_a), kBmThreads / 64);
+  const int64_t nblk_a = ceil_div(nqg * ceil_div(nr, rpw_a), K2A_W);
   if (nblk > INT32_MAX || nblk_a > INT32_MAX) CM_FAIL(CM_EUNSUPPORTED, "BM25 batch too large");
   const int32_t *head_id = h->nhead ? h->head_id.as<int32_t>() : (const int32_t *)nullptr;
   // the gate: the preparation above (descriptors, postings bounds, seeded threshold) overlaps the
   // caller's producer kernels; the scoring kernels wait for it (cm_bm25_search_dev_gated)
   if (gate) CM_HIP(hipStreamWaitEvent(st, gate, 0));
+#if K2A_TRACE
+  if (prune) {  // one record per K2a work unit, zeroed per launch (a unit that has no ranges leaves zeros)
+    if ((rc = g_k2a_trace_buf.ensure((size_t)nblk_a * K2A_W * 32))) return rc;
+    g_k2a_trace_units = nblk_a * K2A_W;
+    uint64_t *tp = g_k2a_trace_buf.as<uint64_t>();
+    CM_HIP(hipMemsetAsync(tp, 0, (size_t)g_k2a_trace_units * 32, st));
+    CM_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_k2a_trace), &tp, sizeof(tp), 0, hipMemcpyHostToDevice, st));
+  }
+#endif
   h->timer.begin(st);  // the search's dominant scoring kernel: K2a (pruned) or K2 (full)
   if (prune) {
     // K2a: exact scores of the tail candidates -> per-range lists; merged lists give each
     // query's k-th best tail score, against which the head-only bound marks the pairs
     // K2 must re-score (cm_bm25_prune.inc)
-    hipLaunchKernelGGL(bm25_tail_kernel<uint16_t>, dim3((unsigned)nblk_a), dim3(kBmThreads), 0, st, q_terms_dev,
+    hipLaunchKernelGGL(bm25_tail_kernel<uint16_t>, dim3((unsigned)nblk_a), dim3(64 * K2A_W), 0, st, q_terms_dev,
                        q_off_dev, nq, h->vocab, w.q_idf, w.bounds, nr, rpw_a, h->post_doc.as<int32_t>(),
                        h->post_tf.as<uint16_t>(), head_id, h->headtf.as<uint8_t>(), h->npad, h->dl.as<int32_t>(),
                        h->live.as<uint32_t>(), allow_dev, avgdl, k, w.cand_key, w.cand_row, w.thr, w.need, w.qd_code,
@@ -1971,6 +1984,18 @@ int64_t cm_bm25_workspace_subblocks(cm_bm25 *h, int32_t nq, int32_t total_terms,
     return -1;
   return n;
 }
+
+#if K2A_TRACE
+// diagnostic builds: the last K2a launch's records, 4 x u64 per work unit (cm_bm25_prune.inc)
+int64_t cm_bm25_k2a_trace(cm_bm25 *h, uint64_t *out, int64_t cap_units) {
+  if (!h || !out) return -1;
+  DeviceGuard dg(h->dev);
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
+  const int64_t n = std::min(cap_units, g_k2a_trace_units);
+  if (n > 0 && hipMemcpy(out, g_k2a_trace_buf.ptr, (size_t)n * 32, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  return g_k2a_trace_units;
+}
+#endif
 
 int cm_bm25_timing(cm_bm25 *h, int32_t enable) {
   if (!h) CM_FAIL(CM_EINVAL, "null handle");

@@ -18,7 +18,7 @@
 // whose tail lists overflow LDS — is re-scored in full by K2, whose complete
 // range list replaces the tail pass's.
 
-// K2a's LDS list capacity and occupancy target: 320 slots (25 KB per 4-wave block) with 5 waves per
+// K2a's LDS list capacity and occupancy target: 320 slots (6.25 KB per wave) with 5 waves per
 // SIMD measured 2.26 vs 2.39 ms for 512 slots at 4 (10M docs, B = 256; bit-identical results);
 // 256 slots overflow often enough that the K2 re-score costs more than the occupancy gains
 #ifndef K2A_CAP
@@ -38,6 +38,14 @@
 #endif
 #ifndef K2A_WPE
 #define K2A_WPE 5
+#endif
+// Waves per K2a block.  The waves never synchronise, but a block gives its LDS back (and lets the
+// next block in) only when its slowest wave ends, and a wave's work is Zipf-skewed (p50 18 us, p99
+// 72 us): 4-wave blocks held 2.6 of the 5 waves per SIMD the kernel is built for, evenly over the
+// whole launch, one-wave blocks hold 3.8 (profiles/k2a_tail.txt).  10M docs, B = 256, alone, same
+// box: 1.128 ms at 4, 0.872 at 2, 0.844 at 1 (profiles/k2a_order_ab.txt; bit-identical results).
+#ifndef K2A_W
+#define K2A_W 1
 #endif
 // 1: K2a's gather-free candidate pre-bound (tail tf at the block's shortest length + the heads'
 // per-block ratio maxima, all LDS / L2-resident) before the per-document head tf / length gathers;
@@ -60,6 +68,15 @@
 // per-term tf slots of K2a's candidate scoring packed two per register (0: one register each)
 #ifndef K2A_PACK
 #define K2A_PACK 1
+#endif
+// diagnostic variant builds only (off in the product; no output depends on it): every K2a wave
+// records {XCC << 32 | unit + 1, start, end (s_memrealtime ticks, 100 MHz), tail postings loaded} for
+// each work unit it runs, read back by cm_bm25_k2a_trace (tools/bm25_probe.py --k2a-trace)
+#ifndef K2A_TRACE
+#define K2A_TRACE 0
+#endif
+#if K2A_TRACE
+__device__ uint64_t *g_k2a_trace;
 #endif
 typedef uint16_t u16x2_t __attribute__((ext_vector_type(2)));
 constexpr int kCandCap = K2A_CAP;  // tail postings per (wave, range) in K2a; more -> K2 re-scores the range
@@ -89,7 +106,7 @@ __device__ inline float ratio_up32(uint32_t tf, float kd) {
   return (t * 2.5f) * __builtin_amdgcn_rcpf(t + kd);
 }
 template <typename TF>
-__global__ void __launch_bounds__(kBmThreads) __attribute__((amdgpu_waves_per_eu(K2A_WPE)))
+__global__ void __launch_bounds__(64 * K2A_W) __attribute__((amdgpu_waves_per_eu(K2A_WPE)))
     bm25_tail_kernel(const int32_t *__restrict__ q_terms, const int32_t *__restrict__ q_off, int nq, int32_t vocab,
                      const double *__restrict__ q_idf, const int64_t *__restrict__ bounds, int nr, int rpw,
                      const int32_t *__restrict__ post_doc, const TF *__restrict__ post_tf,
@@ -104,7 +121,7 @@ __global__ void __launch_bounds__(kBmThreads) __attribute__((amdgpu_waves_per_eu
                      const uint8_t *__restrict__ blk_maxtf, const int32_t *__restrict__ blk_mindl,
                      double maxr_avgdl, int64_t nblk, const uint8_t *__restrict__ head_maxtf,
                      const int32_t *__restrict__ range_mindl, int dbg, const uint8_t *__restrict__ blk16_maxr) {
-  constexpr int W = kBmThreads / 64;
+  constexpr int W = K2A_W;
   const double avgdl = *avgdl_p;
   // the candidates' pre-bound (below): per-(head, 64-doc block) ratio maxima, valid for a search
   // avgdl up to the one they were built at; otherwise the block's largest head tf byte
@@ -142,6 +159,10 @@ __global__ void __launch_bounds__(kBmThreads) __attribute__((amdgpu_waves_per_eu
   const int rg = wid / nqg;
   const int r0 = rg * rpw, r1 = min(r0 + rpw, nr);
   if (r0 >= r1) return;  // whole wave
+#if K2A_TRACE
+  const uint64_t tr_t0 = __builtin_amdgcn_s_memrealtime();
+  uint64_t tr_post = 0;
+#endif
   const int nqw = min(kQPerWave, nq - q0);
   int32_t *pdoc = s_pdoc[wave];
   uint16_t *ptf = s_ptf[wave];
@@ -211,6 +232,9 @@ __global__ void __launch_bounds__(kBmThreads) __attribute__((amdgpu_waves_per_eu
       if (tail) my_hi = bounds[(int64_t)my_i * bstride + r + nsub];
       scan_counts(cnt, excl, n_tot);
     }
+#if K2A_TRACE
+    tr_post += (uint64_t)n_tot;
+#endif
     int64_t nx_hi = my_hi;
     if (r + nsub < r1 && tail) nx_hi = bounds[(int64_t)my_i * bstride + min(r + nsub + SUB, r1)];
     uint64_t Tv = kEmptyKey;
@@ -616,6 +640,16 @@ __global__ void __launch_bounds__(kBmThreads) __attribute__((amdgpu_waves_per_eu
     my_hi = nx_hi;
     r += nsub;
   }
+#if K2A_TRACE
+  if (lane == 0) {
+    uint64_t *tr = g_k2a_trace + 4 * (int64_t)wid;
+    const uint64_t xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;  // XCC_ID[3:0]
+    tr[0] = (xcc << 32) | (uint64_t)(wid + 1);
+    tr[1] = tr_t0;
+    tr[2] = __builtin_amdgcn_s_memrealtime();
+    tr[3] = tr_post;
+  }
+#endif
 }
 
 // Re-score planning after the tail pass.  top_score / top_row are the merged tail-pass lists,

@@ -70,7 +70,7 @@ constexpr int kQMeta = 4;         // LDS slots of 1 KiB for the tiles' row scale
 // K1q's LDS budget: ring + metadata slots + staging + counters, in two footprints.  The full 160 KiB
 // (the most staging: fewest processing passes) when the scan has the GPU to itself; 131 KiB when the
 // caller runs other work beside it (the deferred search of the hybrid step, cm_dense_search_dev_deferred):
-// it leaves room for one BM25 block (K2a 26.5 KiB, K2b 28.2 KiB) beside every K1q workgroup, so the
+// it leaves room for one BM25 block (K2b 28.2 KiB; K2a's one-wave blocks 6.7 KiB each) beside every K1q workgroup, so the
 // BM25 stream overlaps the scan on the same CUs instead of waiting for K1q's last workgroup
 // (headline step 8.48 -> 8.31 ms with the 256-thread BM25 merge, profiles/r05_lds_ab.txt)
 #ifndef K1Q_LDS
