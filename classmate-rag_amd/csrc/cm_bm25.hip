@@ -1529,8 +1529,12 @@ void bm25_free(cm_bm25 *h) {
 // Host-array search with k > kMaxTopK: full per-document scores (bm25_scatter_term_kernel, query
 // term order), a stable radix sort by (score desc) over the documents in row order (ties keep the
 // lower row first, zero scores pad in insertion order: quirk Q1), the first k candidates.
+// n_cand may exceed this index's own candidates (a shard scored with global statistics): only the
+// index's ndocs sorted entries exist, and those of rows outside the candidates carry kEmptyKey and
+// come out as (0.0, -1) like the padding.  out_n[i] (optional) = entries of query i with row >= 0.
 int bm25_search_full(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_off, int nq, int k, const double *q_idf,
-                     double avgdl, const uint32_t *allow_dev, int64_t n_cand, double *out_score, int64_t *out_row) {
+                     double avgdl, const uint32_t *allow_dev, int64_t n_cand, double *out_score, int64_t *out_row,
+                     int32_t *out_n) {
   const int64_t n = std::max<int64_t>(h->ndocs, 1);
   int rc;
   size_t tmp_bytes = 0;
@@ -1545,7 +1549,7 @@ int bm25_search_full(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_off, i
   uint64_t *skeys = reinterpret_cast<uint64_t *>(base + off1 + 2 * round_up(n * 8, 256));
   int32_t *rows = reinterpret_cast<int32_t *>(base + off1 + 3 * round_up(n * 8, 256));
   int32_t *srows = rows + round_up(n * 4, 256) / 4;
-  const int64_t kk = std::min<int64_t>(k, n_cand);
+  const int64_t kk = std::min<int64_t>(std::min<int64_t>(k, n_cand), h->ndocs);
   std::vector<uint64_t> hk((size_t)std::max<int64_t>(kk, 1));
   std::vector<int32_t> hr((size_t)std::max<int64_t>(kk, 1));
   for (int i = 0; i < nq; ++i) {
@@ -1571,11 +1575,14 @@ int bm25_search_full(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_off, i
       CM_HIP(hipMemcpyAsync(hr.data(), srows, (size_t)kk * 4, hipMemcpyDeviceToHost, h->stream));
     }
     CM_HIP(hipStreamSynchronize(h->stream));
+    int32_t nv = 0;
     for (int j = 0; j < k; ++j) {
-      const bool ok = j < kk;
+      const bool ok = j < kk && hk[j] != kEmptyKey;
       out_score[(int64_t)i * k + j] = ok ? f64_unorder(~hk[j]) : 0.0;
       out_row[(int64_t)i * k + j] = ok ? (int64_t)hr[j] : -1;
+      nv += ok;
     }
+    if (out_n) out_n[i] = nv;
   }
   return CM_OK;
 }
@@ -2171,12 +2178,8 @@ static int bm25_search_scored(cm_bm25 *h, const int32_t *q_terms, const int32_t 
                               int64_t n_cand, double *out_score, int64_t *out_row, int32_t *out_n) {
   int rc;
   if (k > kMaxTopK) {  // beyond the fused top-k lists: full scores + one sort per query
-    rc = bm25_search_full(h, q_terms, q_off, nq, k, q_idf_host, avgdl, allow_dev, n_cand, out_score, out_row);
+    rc = bm25_search_full(h, q_terms, q_off, nq, k, q_idf_host, avgdl, allow_dev, n_cand, out_score, out_row, out_n);
     if (rc) return rc;
-    if (out_n) {
-      const int32_t nv = (int32_t)std::min<int64_t>(k, n_cand);
-      for (int i = 0; i < nq; ++i) out_n[i] = nv;
-    }
     h->last_rescored = -1;
     return CM_OK;
   }
@@ -2201,9 +2204,12 @@ static int bm25_search_scored(cm_bm25 *h, const int32_t *q_terms, const int32_t 
   CM_HIP(hipMemcpyAsync(out_score, d_score, (size_t)nq * k * 8, hipMemcpyDeviceToHost, h->stream));
   CM_HIP(hipMemcpyAsync(out_row, d_row, (size_t)nq * k * 8, hipMemcpyDeviceToHost, h->stream));
   CM_HIP(hipStreamSynchronize(h->stream));
-  if (out_n) {
-    const int32_t nv = (int32_t)std::min<int64_t>(k, n_cand);
-    for (int i = 0; i < nq; ++i) out_n[i] = nv;
+  if (out_n) {  // the merge pads with row -1 past the index's own candidates (n_cand may be a global count)
+    for (int i = 0; i < nq; ++i) {
+      int32_t nv = 0;
+      for (int j = 0; j < k; ++j) nv += out_row[(int64_t)i * k + j] >= 0;
+      out_n[i] = nv;
+    }
   }
   return CM_OK;
 }

@@ -284,7 +284,10 @@ int cm_bm25_search(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_off, int
  * nullable) restricts the scored documents.  A corpus sharded over several devices in one process
  * (classmate_hip/multidev.py, SURVEY §8(b) Threading / §8(e)) scores every shard with the GLOBAL
  * statistics -- for a where-filter the statistics of the filtered candidates of all shards (quirk
- * Q2, rag/retrieval/bm25.py:184-191) -- and merges the shards' lists by (score desc, row asc). */
+ * Q2, rag/retrieval/bm25.py:184-191) -- and merges the shards' lists by (score desc, row asc).
+ * n_cand may therefore exceed this index's own candidates (its live docs with the allow bit set):
+ * the output then holds only those, every further entry is (score 0.0, row -1), and out_n[i]
+ * counts the entries of query i with row >= 0 (local valid entries, not min(k, n_cand)). */
 int cm_bm25_search_idf(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_off, int32_t nq, int32_t k,
                        const uint32_t *allow_bits, const double *q_idf, double avgdl, int64_t n_cand,
                        double *out_score, int64_t *out_row, int32_t *out_n);

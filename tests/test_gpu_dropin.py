@@ -335,13 +335,10 @@ def test_vector_store_save_after_trailing_deletes(corpus, tmp_path):
     assert [r["id"] for r in GpuVectorStore(persist_dir=tmp_path).query(query_embeddings=emb[0], top_k=3)] == ["new"]
 
 
-@pytest.mark.parametrize("top_k", [300, 999, 5000, -7])
-def test_top_k_beyond_fused_lists(stores, corpus, top_k):
-    """top_k above cm_max_topk() (256): the reference sorts every candidate (bm25.py:199) and passes
-    any n_results to Chroma (vector_chroma.py:225-229); the device full-order path returns the
-    same lists (BM25 bit-exact incl. zero-score padding; dense within 1e-4, exact-oracle order)."""
+def check_top_k_beyond_fused_lists(vs, bm, corpus, top_k):
+    """The assertions of test_top_k_beyond_fused_lists on the given stores (shared with the sharded
+    run in test_gpu_shard_edges.py)."""
     from oracle import ref_semantics as orc
-    vs, bm, _ = stores
     obm = orc.BM25Oracle()
     obm.upsert_many(corpus["ids"], corpus["texts"], corpus["metas"])
     for q in corpus["qtexts"][:3]:
@@ -365,6 +362,15 @@ def test_top_k_beyond_fused_lists(stores, corpus, top_k):
                     assert g["id"] == w["id"]
             idx = {i: n for n, i in enumerate(corpus["ids"])}
             assert all(np.array_equal(r["embedding"], corpus["emb"][idx[r["id"]]]) for r in got[:50])
+
+
+@pytest.mark.parametrize("top_k", [300, 999, 5000, -7])
+def test_top_k_beyond_fused_lists(stores, corpus, top_k):
+    """top_k above cm_max_topk() (256): the reference sorts every candidate (bm25.py:199) and passes
+    any n_results to Chroma (vector_chroma.py:225-229); the device full-order path returns the
+    same lists (BM25 bit-exact incl. zero-score padding; dense within 1e-4, exact-oracle order)."""
+    vs, bm, _ = stores
+    check_top_k_beyond_fused_lists(vs, bm, corpus, top_k)
 
 
 @pytest.mark.parametrize("top_k", [10, 3, 0, -4])

@@ -173,18 +173,31 @@ def test_sharded_hip_bm25_filtered_equals_unsharded_oracle(results, k):
             assert np.array_equal(S, sc)
 
 
+MERGE_SHAPES = [
+    (2, 24, 10), (3, 24, 10), (8, 24, 10),      # <= 192 entries per kind: one entry per thread
+    (4, 256, 1),                                 # multidev's dense merge: 1024 / 4 entries
+    (4, 1, 256),                                 # multidev's BM25 merge: 4 / 1024 entries
+    (3, 100, 7),                                 # 300 / 21: no multiple of the 256 threads
+    (8, 256, 256),                               # 2048 / 2048
+    (16, 256, 256),                              # 4096 / 4096: exactly the kernel's limit
+]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("ws", [2, 3, 8])
-def test_shard_merge_kernel_equals_torch_merge(ws):
+@pytest.mark.parametrize("ws,P,K", MERGE_SHAPES)
+def test_shard_merge_kernel_equals_torch_merge(ws, P, K):
     """the N > 1 step's merge of the packed all-gather runs as one hand-written kernel
     (cm_shard_merge_topk_dev); it must give exactly the torch merge's lists (parallel.merge_packed on
     host tensors, merge_dense_topk / merge_bm25_topk's rules): (distance, row) ascending; (score desc,
     row asc) with -0.0 == 0.0; -1 pads after every real entry -- incl. equal distances / scores
-    across shards and shards with fewer live entries than the list length."""
+    across shards and shards with fewer live entries than the list length.  The shapes go past one
+    entry per thread (ws x P, ws x K > 256: the strided loops advance) up to the 4096-entry limit,
+    and a few queries have nothing but pads in every shard's lists."""
     import torch
     from classmate_hip import parallel as Pl
     rng = np.random.default_rng(ws)
-    B, P, K = 64, 24, 10
+    B = 64
+    all_pads = [5, 17, 40, B - 1]                         # queries whose lists are pads in every shard
     packs = []
     for g in range(ws):
         d = np.sort(rng.choice(np.linspace(0.1, 0.9, 40), (B, P)).astype(np.float32), axis=1)   # ties
@@ -195,10 +208,12 @@ def test_shard_merge_kernel_equals_torch_merge(ws):
         br = rng.permutation(1_000_000)[: B * K].reshape(B, K).astype(np.int64) * ws + g
         o = np.lexsort((br, -s), axis=1)
         s, br = np.take_along_axis(s, o, 1), np.take_along_axis(br, o, 1)
-        npad = rng.integers(0, P // 2, B)                 # short shard lists: pads at the end
+        npad = rng.integers(0, max(P, K) // 2, B)         # short shard lists: pads at the end
+        npad[all_pads] = max(P, K)
         for i in range(B):
-            if npad[i]:
-                d[i, P - npad[i]:], r[i, P - npad[i]:] = 0.0, -1
+            m = min(npad[i], P)
+            if m:
+                d[i, P - m:], r[i, P - m:] = 0.0, -1
             m = min(npad[i], K)
             if m:
                 s[i, K - m:], br[i, K - m:] = 0.0, -1
@@ -211,3 +226,31 @@ def test_shard_merge_kernel_equals_torch_merge(ws):
     torch.cuda.synchronize()
     for w, gt in zip(want, got):
         assert torch.equal(w, gt.cpu()), (w[:2], gt[:2])
+    assert (want[1][all_pads] == -1).all() and (want[3][all_pads] == -1).all()
+    n_real = (allp[:, :, P:2 * P] >= 0).sum((0, 2))      # the real entries come first, every one of them
+    assert torch.equal((got[1].cpu() >= 0).sum(1), n_real.clamp(max=P))
+
+
+@pytest.mark.gpu
+def test_shard_merge_kernel_refuses_more_than_4096_entries():
+    """ws x P = 4097 is one entry past the kernel's LDS arrays: CM_EUNSUPPORTED (RuntimeError) and
+    no launch -- the outputs keep what they held."""
+    import torch
+    from classmate_hip import _lib as L, parallel as Pl
+    from classmate_hip.engine import _stream
+    ws, B, P, K = 17, 2, 241, 1
+    assert ws * P == 4097
+    allp = torch.full((ws, B, 2 * P + 2 * K), -1, dtype=torch.int64, device="cuda")
+    with pytest.raises(RuntimeError):
+        Pl.merge_packed(allp, P, K)
+    with pytest.raises(RuntimeError):
+        Pl.merge_packed(allp, K, P)                       # the same width read as P = 1, K = 241
+    d = torch.full((B, P), 7.0, dtype=torch.float32, device="cuda")
+    r = torch.full((B, P), 7, dtype=torch.int64, device="cuda")
+    s = torch.full((B, K), 7.0, dtype=torch.float64, device="cuda")
+    br = torch.full((B, K), 7, dtype=torch.int64, device="cuda")
+    rc = L.fn["cm_shard_merge_topk_dev"](L.ptr(allp), ws, B, P, K, L.ptr(d), L.ptr(r), L.ptr(s), L.ptr(br),
+                                         _stream(allp.device.index))
+    assert rc == L.CM_EUNSUPPORTED
+    torch.cuda.synchronize()
+    assert (d == 7.0).all() and (r == 7).all() and (s == 7.0).all() and (br == 7).all()
