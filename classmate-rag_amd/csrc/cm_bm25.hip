@@ -331,11 +331,11 @@ template <typename TF>
 __global__ void __launch_bounds__(kBmThreads) __attribute__((amdgpu_waves_per_eu(K2_WAVES_PER_EU)))
     bm25_range_kernel(const int32_t *__restrict__ q_terms, const int32_t *__restrict__ q_off, int nq,
                       const double *__restrict__ q_idf, const int64_t *__restrict__ bounds, int nr, int rpw,
-                      const int64_t *__restrict__ term_off, const int32_t *__restrict__ post_doc,
-                      const TF *__restrict__ post_tf, const int32_t *__restrict__ head_id,
-                      const uint8_t *__restrict__ headtf, int64_t npad, const int32_t *__restrict__ dl,
-                      const uint32_t *__restrict__ live, const uint32_t *__restrict__ allow, int64_t ndocs,
-                      const double *__restrict__ avgdl_p, const double *__restrict__ lut, int lut_dmin, int k,
+                      const int32_t *__restrict__ post_doc, const TF *__restrict__ post_tf,
+                      const int32_t *__restrict__ head_id, const uint8_t *__restrict__ headtf, int64_t npad,
+                      const int32_t *__restrict__ dl, const uint32_t *__restrict__ live,
+                      const uint32_t *__restrict__ allow, int64_t ndocs, const double *__restrict__ avgdl_p,
+                      const double *__restrict__ lut, int lut_dmin, int k,
                       uint64_t *__restrict__ cand_key, uint32_t *__restrict__ cand_row,
                       unsigned long long *__restrict__ thr_key, const uint8_t *__restrict__ need, int32_t vocab,
                       int dbg) {
@@ -1458,17 +1458,10 @@ int bm25_launch_core(cm_bm25 *h, const int32_t *q_terms_dev, const int32_t *q_of
     // K2a: exact scores of the tail candidates -> per-range lists; merged lists give each
     // query's k-th best tail score, against which the head-only bound marks the pairs
     // K2 must re-score (cm_bm25_prune.inc)
-    hipLaunchKernelGGL(bm25_tail_kernel<uint16_t>, dim3((unsigned)nblk_a), dim3(64 * K2A_W), 0, st, q_terms_dev,
-                       q_off_dev, nq, h->vocab, w.q_idf, w.bounds, nr, rpw_a, h->post_doc.as<int32_t>(),
-                       h->post_tf.as<uint16_t>(), head_id, h->headtf.as<uint8_t>(), h->npad, h->dl.as<int32_t>(),
-                       h->live.as<uint32_t>(), allow_dev, avgdl, k, w.cand_key, w.cand_row, w.thr, w.need, w.qd_code,
-                       w.qd_term, w.qd_idf, w.qd_tb, w.qd_len,
-                       (h->nhead && h->maxr_avgdl > 0.0) ? h->blk_maxr.as<uint8_t>() : (const uint8_t *)nullptr,
-                       h->nhead ? h->blk_maxtf.as<uint8_t>() : (const uint8_t *)nullptr, h->blk_mindl.as<int32_t>(),
-                       h->maxr_avgdl, (int64_t)nr * (kRange / 64),
-                       h->nhead ? h->head_maxtf.as<uint8_t>() : (const uint8_t *)nullptr, h->range_mindl.as<int32_t>(),
-                       bm25_debug_flags(),
-                       (h->nhead && h->maxr_avgdl > 0.0) ? h->blk16_maxr.as<uint8_t>() : (const uint8_t *)nullptr);
+    hipLaunchKernelGGL(bm25_tail_kernel<uint16_t>, dim3((unsigned)nblk_a), dim3(64 * K2A_W), 0, st, nq, w.bounds, nr,
+                       rpw_a, h->post_doc.as<int32_t>(), h->post_tf.as<uint16_t>(), h->headtf.as<uint8_t>(), h->npad,
+                       h->dl.as<int32_t>(), h->live.as<uint32_t>(), allow_dev, avgdl, k, w.cand_key, w.cand_row, w.thr,
+                       w.need, w.qd_code, w.qd_term, w.qd_idf, w.qd_tb, w.qd_len, bm25_debug_flags());
     h->timer.end(st);
     CM_HIP(hipGetLastError());
     if ((rc = launch_bm25_merge(w.cand_key, w.cand_row, nq, nr, k, score_dev, row_dev, st))) return rc;
@@ -1493,7 +1486,7 @@ int bm25_launch_core(cm_bm25 *h, const int32_t *q_terms_dev, const int32_t *q_of
     CM_HIP(hipGetLastError());
   }
   hipLaunchKernelGGL(bm25_range_kernel<uint16_t>, dim3((unsigned)nblk), dim3(kBmThreads), 0, st, q_terms_dev,
-                     q_off_dev, nq, w.q_idf, w.bounds, nr, rpw, h->term_off.as<int64_t>(), h->post_doc.as<int32_t>(),
+                     q_off_dev, nq, w.q_idf, w.bounds, nr, rpw, h->post_doc.as<int32_t>(),
                      h->post_tf.as<uint16_t>(), head_id, h->headtf.as<uint8_t>(), h->npad, h->dl.as<int32_t>(),
                      h->live.as<uint32_t>(), allow_dev, h->ndocs, avgdl, w.lut, h->lut_dmin, k, w.cand_key,
                      w.cand_row, w.thr, prune ? (const uint8_t *)w.need : (const uint8_t *)nullptr, h->vocab,

@@ -47,28 +47,18 @@
 #ifndef K2A_W
 #define K2A_W 1
 #endif
-// 1: K2a's gather-free candidate pre-bound (tail tf at the block's shortest length + the heads'
-// per-block ratio maxima, all LDS / L2-resident) before the per-document head tf / length gathers;
-// 0: the round-4 order (gathers first).  Measured round 5 (profiles/r05_k2a_prebound_ab.txt, 10M x
-// B = 256, same box): 2.055 vs 1.377 ms standalone, 28.4k vs 31.3k q/s in the step -- the running
-// threshold T is too weak while the lists fill, so most candidates pass the pre-bound and then pay
-// both load levels (and 2 spilled VGPRs); kept as an A/B knob, off
-#ifndef K2A_PREB
-#define K2A_PREB 0
-#endif
-// 1: K2a gathers a candidate's length only when its bound at the 64-doc block's shortest length reaches T
-#ifndef K2A_DLB
-#define K2A_DLB 0
-#endif
-// 1: K2a's fp32 candidate bound adds every slot branch-free (a zero tf adds +0.0 exactly: same bits) instead
-// of one exec-mask branch per slot (A/B knob)
-#ifndef K2A_BF
-#define K2A_BF 0
-#endif
-// per-term tf slots of K2a's candidate scoring packed two per register (0: one register each)
-#ifndef K2A_PACK
-#define K2A_PACK 1
-#endif
+// K2a's candidate scoring has one path: packed head tf gathers and the length load issued up
+// front, tail tf from the LDS lists, the fp32 bound against T, the fp64 score.  Variants that were
+// built, measured slower and removed (the commit before their removal is the last that builds them):
+//  * a gather-free pre-bound before the gathers, from per-(head, 64-doc block) bytes (2.06 vs 1.38
+//    ms, profiles/r05_k2a_prebound_ab.txt), from range-level bounds in LDS and from 16-doc
+//    sub-block bytes (1.75 vs 1.13 ms): DESIGN.md §6 "Measured and not adopted" and §9 item 4,
+//    profiles/r05_bm25_tseed_ab.txt, profiles/r06_seed_sample_k2a_prebound_ab.txt;
+//  * the length gather behind a bound at the block's shortest length (same §6 paragraph and
+//    r05 profile), and a branch-free fp32 sum (profiles/r06_k2b_uniform_ab.txt);
+//  * one register per term tf instead of two per register (profiles/r04c_k2a_pack_ab.txt).
+// Every bound placed before the gathers serialises their latency; the others cost spilled VGPRs.
+
 // diagnostic variant builds only (off in the product; no output depends on it): every K2a wave
 // records {XCC << 32 | unit + 1, start, end (s_memrealtime ticks, 100 MHz), tail postings loaded} for
 // each work unit it runs, read back by cm_bm25_k2a_trace (tools/bm25_probe.py --k2a-trace)
@@ -107,27 +97,18 @@ __device__ inline float ratio_up32(uint32_t tf, float kd) {
 }
 template <typename TF>
 __global__ void __launch_bounds__(64 * K2A_W) __attribute__((amdgpu_waves_per_eu(K2A_WPE)))
-    bm25_tail_kernel(const int32_t *__restrict__ q_terms, const int32_t *__restrict__ q_off, int nq, int32_t vocab,
-                     const double *__restrict__ q_idf, const int64_t *__restrict__ bounds, int nr, int rpw,
+    bm25_tail_kernel(int nq, const int64_t *__restrict__ bounds, int nr, int rpw,
                      const int32_t *__restrict__ post_doc, const TF *__restrict__ post_tf,
-                     const int32_t *__restrict__ head_id, const uint8_t *__restrict__ headtf, int64_t npad,
+                     const uint8_t *__restrict__ headtf, int64_t npad,
                      const int32_t *__restrict__ dl, const uint32_t *__restrict__ live,
                      const uint32_t *__restrict__ allow, const double *__restrict__ avgdl_p, int k,
                      uint64_t *__restrict__ cand_key, uint32_t *__restrict__ cand_row,
                      unsigned long long *__restrict__ thr_key, uint8_t *__restrict__ need,
                      const int32_t *__restrict__ qd_code, const int32_t *__restrict__ qd_term,
                      const double *__restrict__ qd_idf, const int32_t *__restrict__ qd_tb,
-                     const int32_t *__restrict__ qd_len, const uint8_t *__restrict__ blk_maxr,
-                     const uint8_t *__restrict__ blk_maxtf, const int32_t *__restrict__ blk_mindl,
-                     double maxr_avgdl, int64_t nblk, const uint8_t *__restrict__ head_maxtf,
-                     const int32_t *__restrict__ range_mindl, int dbg, const uint8_t *__restrict__ blk16_maxr) {
+                     const int32_t *__restrict__ qd_len, int dbg) {
   constexpr int W = K2A_W;
   const double avgdl = *avgdl_p;
-  // the candidates' pre-bound (below): per-(head, 64-doc block) ratio maxima, valid for a search
-  // avgdl up to the one they were built at; otherwise the block's largest head tf byte
-  const bool use_r = blk_maxr != nullptr && avgdl <= maxr_avgdl;
-  const uint8_t *blk_h = use_r ? blk_maxr : blk_maxtf;
-  (void)blk_h;
 #ifndef CM_ABLATION
   dbg = 0;  // product build: the ablation branches fold away
 #endif
@@ -138,12 +119,7 @@ __global__ void __launch_bounds__(64 * K2A_W) __attribute__((amdgpu_waves_per_eu
   __shared__ int32_t s_t[W][64], s_h[W][64], s_off[W][64], s_cnt[W][64];
   __shared__ double s_idf[W][64];
   __shared__ float s_fi[W][64];  // idf rounded up to fp32 (0 when <= 0) for the candidates' bound
-  __shared__ float s_hk[W][64];  // pre-bound: 1/102 for a head slot bounded by its block ratio byte, else 0
   __shared__ double s_tq[W][kQPerWave];  // per query of the wave: T of this iteration (score)
-#if K2A_PREB == 2
-  __shared__ float s_hb[W][K2A_SUB][64];  // per (sub-range, term slot): a head slot's bound idf . ratio(maxtf, mindl)
-  __shared__ float s_kdr[W][K2A_SUB];     // per sub-range: K_d lower bound at its shortest document
-#endif
   const float inv_avg = inv_avg_lo(avgdl);
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -204,7 +180,6 @@ __global__ void __launch_bounds__(64 * K2A_W) __attribute__((amdgpu_waves_per_eu
   sh[lane] = my_h;
   sidf[lane] = my_idf;
   s_fi[wave][lane] = idf_up(my_idf);
-  s_hk[wave][lane] = (use_r && my_h >= 0) ? (1.0f / 102.0f) : 0.0f;
   constexpr int SUB = K2A_SUB;
   constexpr int NG = kQPerWave * SUB;  // (query, range) groups of one iteration: g = q * SUB + sub
   int64_t my_lo = 0, my_hi = 0;
@@ -258,14 +233,6 @@ __global__ void __launch_bounds__(64 * K2A_W) __attribute__((amdgpu_waves_per_eu
     if (lane < nsub) need[(int64_t)qg * nr + r + lane] = 0;
     soff[lane] = excl;
     scnt[lane] = cnt;
-#if K2A_PREB == 2
-    // the iteration's range-level bounds (L2-resident bytes, loaded once per wave and sub-range)
-    for (int sb = 0; sb < nsub; ++sb) {
-      const float kdr = kd_lo32(range_mindl[r + sb], inv_avg);
-      s_hb[wave][sb][lane] = my_h >= 0 ? s_fi[wave][lane] * ratio_up32(head_maxtf[(int64_t)my_h * nr + r + sb], kdr) : 0.0f;
-      if (lane == 0) s_kdr[wave][sb] = kdr;
-    }
-#endif
     // ---- the range's tail postings of the wave's queries -> LDS (list-major, doc-sorted)
     for (int e0 = 0; e0 < n_tot; e0 += 64) {
       const int e = e0 + lane;
@@ -301,148 +268,10 @@ __global__ void __launch_bounds__(64 * K2A_W) __attribute__((amdgpu_waves_per_eu
         else if (!(dbg & 128) && scnt[l2] > 0 && lds_find(pdoc + soff[l2], scnt[l2], d) >= 0) own = false;
       }
       if (own) {
-        // Pre-bound without HBM gathers (VERDICT r4 #4).  A candidate's score is at most
-        //   sum over tail terms of idf . ratio(tf, K_d(block's shortest document))   (tf from LDS)
-        // + sum over head terms of idf . (the head's per-block ratio maximum)      (L2-resident bytes)
-        // and below the query's running threshold T its exact score is too: the per-document head tf
-        // bytes and length -- one 64-B HBM sector each, K2a's excess traffic -- are then never read.
-        // The head slots first hold the block bound bytes, overwritten by the real tf bytes when the
-        // candidate passes (same 8 registers).
-#if K2A_PREB == 2
-        // Range-level pre-bound, no per-candidate global load: tail tf from the LDS lists at the
-        // sub-range's shortest length + each head slot's range bound (LDS); below T the document's
-        // head tf bytes and length are never gathered
-#if K2A_PACK
-        u16x2_t tfp[kTermLanes / 2];
-#pragma unroll
-        for (int jj = 0; jj < kTermLanes / 2; ++jj) tfp[jj] = u16x2_t{0, 0};
-        auto tf_get = [&](int jj) __attribute__((always_inline)) -> uint32_t { return tfp[jj >> 1][jj & 1]; };
-        auto tf_set = [&](int jj, uint32_t v) __attribute__((always_inline)) { tfp[jj >> 1][jj & 1] = (uint16_t)v; };
-#else
-        uint32_t tfv[kTermLanes];
-#pragma unroll
-        for (int jj = 0; jj < kTermLanes; ++jj) tfv[jj] = 0u;
-        auto tf_get = [&](int jj) __attribute__((always_inline)) -> uint32_t { return tfv[jj]; };
-        auto tf_set = [&](int jj, uint32_t v) __attribute__((always_inline)) { tfv[jj] = v; };
-#endif
-#pragma unroll
-        for (int jj = 0; jj < kTermLanes; ++jj) {  // tail terms' tf from the LDS lists
-          const int l2 = qb + jj;
-          const int32_t t2 = st[l2];
-          if (t2 < 0 || sh[l2] >= 0) continue;
-          if (t2 == tj) {
-            tf_set(jj, ptf[e]);
-          } else {
-            const int c = (dbg & 256) ? 0 : scnt[l2];
-            if (c > 0) {
-              const int o = soff[l2];
-              const int xx = lds_find(pdoc + o, c, d);
-              if (xx >= 0) tf_set(jj, ptf[o + xx]);
-            }
-          }
-        }
-        const double Tq = s_tq[wave][qb / kTermLanes];
-        const int sub = (d >> 10) - r;
-        const float kdr = s_kdr[wave][sub];
-        float ub0 = 0.0f;
-#pragma unroll
-        for (int jj = 0; jj < kTermLanes; ++jj) {
-          const int l2 = qb + jj;
-          if (sh[l2] >= 0) ub0 += s_hb[wave][sub][l2];
-          else if (tf_get(jj)) ub0 += s_fi[wave][l2] * ratio_up32(tf_get(jj), kdr);
-        }
-        bool pass = !((double)(ub0 * kPlanSlack) < Tq);
-        int32_t dlen = 0;
-        if (pass) {   // the document's own head tf bytes and length
-#pragma unroll
-          for (int jj = 0; jj < kTermLanes; ++jj) {
-            const int32_t hh = sh[qb + jj];
-            if (hh >= 0) tf_set(jj, (dbg & 64) ? 1u : (uint32_t)headtf[(int64_t)hh * npad + d]);
-          }
-          dlen = (dbg & 512) ? 120 : dl[d];
-          float ub = 0.0f;
-          const float kd32 = kd_lo32(dlen, inv_avg);
-#pragma unroll
-          for (int jj = 0; jj < kTermLanes; ++jj)
-            if (tf_get(jj)) ub += s_fi[wave][qb + jj] * ratio_up32(tf_get(jj), kd32);
-          pass = !((double)(ub * kPlanSlack) < Tq);
-        }
-#elif K2A_PREB
-        const int64_t blk = d >> 6;
-        // K2A_PREB 3: the head bound bytes of the candidate's 16-doc sub-block (blk16_maxr, q / 102):
-        // a super-range's candidates of one query share those bytes' few lines, unlike the tf gathers
-        const bool u16 = K2A_PREB == 3 && use_r && blk16_maxr != nullptr;
-        const uint8_t *bhp = u16 ? blk16_maxr : blk_h;
-        const int64_t bstr = u16 ? nblk * 4 : nblk, bidx = u16 ? (int64_t)(d >> 4) : blk;
-#if K2A_PACK
-        // the 16 term tf values as 16-bit halves of 8 registers (head bytes land by d16 loads,
-        // tail tf are u16): half the VGPRs of one register per term
-        u16x2_t tfp[kTermLanes / 2];
-#pragma unroll
-        for (int jj = 0; jj < kTermLanes; ++jj) {  // head block-bound bytes: independent loads, issued together
-          const int32_t hh = sh[qb + jj];
-          tfp[jj >> 1][jj & 1] = hh >= 0 ? (uint16_t)bhp[(int64_t)hh * bstr + bidx] : (uint16_t)0;
-        }
-        auto tf_get = [&](int jj) __attribute__((always_inline)) -> uint32_t { return tfp[jj >> 1][jj & 1]; };
-        auto tf_set = [&](int jj, uint32_t v) __attribute__((always_inline)) { tfp[jj >> 1][jj & 1] = (uint16_t)v; };
-#else
-        uint32_t tfv[kTermLanes];
-#pragma unroll
-        for (int jj = 0; jj < kTermLanes; ++jj) {
-          const int32_t hh = sh[qb + jj];
-          tfv[jj] = hh >= 0 ? (uint32_t)bhp[(int64_t)hh * bstr + bidx] : 0u;
-        }
-        auto tf_get = [&](int jj) __attribute__((always_inline)) -> uint32_t { return tfv[jj]; };
-        auto tf_set = [&](int jj, uint32_t v) __attribute__((always_inline)) { tfv[jj] = v; };
-#endif
-        const float kdb = kd_lo32(blk_mindl[blk], inv_avg);
-#pragma unroll
-        for (int jj = 0; jj < kTermLanes; ++jj) {  // tail terms' tf from the LDS lists
-          const int l2 = qb + jj;
-          const int32_t t2 = st[l2];
-          if (t2 < 0 || sh[l2] >= 0) continue;
-          if (t2 == tj) {
-            tf_set(jj, ptf[e]);
-          } else {
-            const int c = (dbg & 256) ? 0 : scnt[l2];
-            if (c > 0) {
-              const int o = soff[l2];
-              const int xx = lds_find(pdoc + o, c, d);
-              if (xx >= 0) tf_set(jj, ptf[o + xx]);
-            }
-          }
-        }
-        const double Tq = s_tq[wave][qb / kTermLanes];
-        // head slots: ratio = q / 102 (use_r) or ratio(max tf byte, K_d lower bound) -- the per-slot
-        // kind is in the sign of s_fi's neighbour table s_hk (1 / 102 or 0)
-        float ub0 = 0.0f;
-#pragma unroll
-        for (int jj = 0; jj < kTermLanes; ++jj) {
-          const uint32_t v = tf_get(jj);
-          const float hk = s_hk[wave][qb + jj];
-          const float rr = hk > 0.0f ? (float)v * hk : ratio_up32(v, kdb);
-          if (v) ub0 += s_fi[wave][qb + jj] * rr;
-        }
-        bool pass = !((double)(ub0 * kPlanSlack) < Tq);
-        int32_t dlen = 0;
-        if (pass) {   // the document's own head tf bytes and length
-#pragma unroll
-          for (int jj = 0; jj < kTermLanes; ++jj) {
-            const int32_t hh = sh[qb + jj];
-            if (hh >= 0) tf_set(jj, (dbg & 64) ? 1u : (uint32_t)headtf[(int64_t)hh * npad + d]);
-          }
-          dlen = (dbg & 512) ? 120 : dl[d];
-          // fp32 upper bound next: below T the exact score is too, and the compaction below would
-          // drop the candidate anyway (same T)
-          float ub = 0.0f;
-          const float kd32 = kd_lo32(dlen, inv_avg);
-#pragma unroll
-          for (int jj = 0; jj < kTermLanes; ++jj)
-            if (tf_get(jj)) ub += s_fi[wave][qb + jj] * ratio_up32(tf_get(jj), kd32);
-          pass = !((double)(ub * kPlanSlack) < Tq);
-        }
-#else   // round-4 order: every candidate's head tf bytes and length gathered up front
-#if K2A_PACK
+        // the 16 term tf values as 16-bit halves of 8 registers (head bytes land by d16 loads, tail
+        // tf are u16): half the VGPRs of one register per term.  Every candidate's head tf bytes
+        // and length are gathered up front; the fp32 upper bound follows: below T the exact score
+        // is too, and the compaction below would drop the candidate anyway (same T)
         u16x2_t tfp[kTermLanes / 2];
 #pragma unroll
         for (int jj = 0; jj < kTermLanes; ++jj) {  // head tf bytes: independent loads, issued together
@@ -452,23 +281,7 @@ __global__ void __launch_bounds__(64 * K2A_W) __attribute__((amdgpu_waves_per_eu
         }
         auto tf_get = [&](int jj) __attribute__((always_inline)) -> uint32_t { return tfp[jj >> 1][jj & 1]; };
         auto tf_set = [&](int jj, uint32_t v) __attribute__((always_inline)) { tfp[jj >> 1][jj & 1] = (uint16_t)v; };
-#else
-        uint32_t tfv[kTermLanes];
-#pragma unroll
-        for (int jj = 0; jj < kTermLanes; ++jj) {
-          const int32_t hh = sh[qb + jj];
-          tfv[jj] = hh >= 0 ? ((dbg & 64) ? 1u : (uint32_t)headtf[(int64_t)hh * npad + d]) : 0u;
-        }
-        auto tf_get = [&](int jj) __attribute__((always_inline)) -> uint32_t { return tfv[jj]; };
-        auto tf_set = [&](int jj, uint32_t v) __attribute__((always_inline)) { tfv[jj] = v; };
-#endif
-#if K2A_DLB
-        // the length gather (a 64-B HBM sector per candidate) waits for a bound at the 64-doc block's
-        // shortest length (blk_mindl: 0.6 MB at 10M, L2-resident), issued with the head tf bytes
-        const int32_t bmin = blk_mindl[d >> 6];
-#else
         const int32_t dlen = (dbg & 512) ? 120 : dl[d];
-#endif
 #pragma unroll
         for (int jj = 0; jj < kTermLanes; ++jj) {  // tail terms' tf from the LDS lists
           const int l2 = qb + jj;
@@ -486,32 +299,12 @@ __global__ void __launch_bounds__(64 * K2A_W) __attribute__((amdgpu_waves_per_eu
           }
         }
         const double Tq = s_tq[wave][qb / kTermLanes];
-#if K2A_DLB
-        float ubb = 0.0f;
-        const float kdb = kd_lo32(bmin, inv_avg);
-#pragma unroll
-        for (int jj = 0; jj < kTermLanes; ++jj)
-          if (tf_get(jj)) ubb += s_fi[wave][qb + jj] * ratio_up32(tf_get(jj), kdb);
-        bool pass = !((double)(ubb * kPlanSlack) < Tq);
-        int32_t dlen = 0;
-        if (pass) {
-          dlen = (dbg & 512) ? 120 : dl[d];
-          float ub = 0.0f;
-          const float kd32 = kd_lo32(dlen, inv_avg);
-#pragma unroll
-          for (int jj = 0; jj < kTermLanes; ++jj)
-            if (tf_get(jj)) ub += s_fi[wave][qb + jj] * ratio_up32(tf_get(jj), kd32);
-          pass = !((double)(ub * kPlanSlack) < Tq);
-        }
-#else
         float ub = 0.0f;
         const float kd32 = kd_lo32(dlen, inv_avg);
 #pragma unroll
         for (int jj = 0; jj < kTermLanes; ++jj)
-          if (K2A_BF || tf_get(jj)) ub += s_fi[wave][qb + jj] * ratio_up32(tf_get(jj), kd32);   // (tf 0 adds +0.0)
+          if (tf_get(jj)) ub += s_fi[wave][qb + jj] * ratio_up32(tf_get(jj), kd32);
         const bool pass = !((double)(ub * kPlanSlack) < Tq);
-#endif
-#endif
         if (pass) {
           const double kd = kd_of(dlen, avgdl);
           double sc = 0.0;
@@ -905,13 +698,6 @@ __device__ inline int k2b_compact(uint64_t *ckey, uint32_t *crow, int n, int k, 
 #ifndef K2B_WPE
 #define K2B_WPE 4
 #endif
-#ifndef K2B_STAT
-#define K2B_STAT 0   // diagnostic variant builds only: per-launch counts of the planned blocks' work (printf)
-#endif
-#if K2B_STAT
-__device__ unsigned long long g_k2b_stat[8];
-__device__ unsigned int g_k2b_done;
-#endif
 #ifndef K2B_ABL  // timing ablations (variant builds only; results invalid): 1 no postings walk,
 #define K2B_ABL 0  // 2 no tile loads, 4 no scoring, 8 no block work at all, 16 integer sum for
 // the fp64 scoring, 32 scoring without the merge, 64 no fp32 pre-bound
@@ -935,20 +721,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K2B_WP
   const uint32_t n_items = *item_count;
   const uint32_t stride = gridDim.x * W;
   uint32_t itx = blockIdx.x * W + wave;
-#if K2B_STAT
-  auto stat_done = [&]() {
-    if (lane == 0 && atomicAdd(&g_k2b_done, 1u) == gridDim.x * W - 1) {
-      unsigned long long *g = g_k2b_stat;
-      printf("K2B_STAT items %u blocks %llu docs_ok %llu docs_above_bound %llu blocks_with_above %llu "
-             "sub16_bound_pass %llu sub16_with_above %llu\n", n_items, g[3], g[0], g[1], g[2], g[4], g[5]);
-      for (int i = 0; i < 8; ++i) g[i] = 0;
-      g_k2b_done = 0;
-    }
-  };
-  if (itx >= n_items) { stat_done(); return; }
-#else
   if (itx >= n_items) return;  // whole wave
-#endif
   const int tl = lane < kTermLanes ? lane : 0;
   const float inv_avg = inv_avg_lo(avgdl);
   uint64_t *ckey = s_ckey[wave], *tkey = s_tkey[wave];
@@ -1071,36 +844,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K2B_WP
           key = score_key(sc);
           if ((K2B_ABL & 32) && sc > -1.0) key = kEmptyKey;  // never merges
         }
-#if K2B_STAT
-        {
-          bool abv = false;
-          const float kdd = kd_lo32(dlv[u], inv_avg);
-          if (ok) abv = !k2b_below(tfv[u], fi, kdd, Tsc, headm);
-          float sub = 0.0f;   // the 16-doc segment's sum over head slots of the largest ratio
-#pragma unroll
-          for (int j = 0; j < kTermLanes; ++j)
-            if ((headm >> j) & 1u) {
-              float rr = ok ? ratio_up32(tfv[u][j], kdd) : 0.0f;
-              rr = fmaxf(rr, __shfl_xor(rr, 1));
-              rr = fmaxf(rr, __shfl_xor(rr, 2));
-              rr = fmaxf(rr, __shfl_xor(rr, 4));
-              rr = fmaxf(rr, __shfl_xor(rr, 8));
-              sub += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(fi), j)) * rr;
-            }
-          const bool sub_pass = !((double)(sub * kPlanSlack) < Tsc);
-          const uint64_t bok = __ballot(ok), babv = __ballot(abv), bsub = __ballot(sub_pass);
-          if (lane == 0) {
-            int segs_abv = 0;
-            for (int sg = 0; sg < 4; ++sg) segs_abv += ((babv >> (16 * sg)) & 0xffffull) ? 1 : 0;
-            atomicAdd(&g_k2b_stat[0], (unsigned long long)__popcll(bok));
-            atomicAdd(&g_k2b_stat[1], (unsigned long long)__popcll(babv));
-            atomicAdd(&g_k2b_stat[2], babv ? 1ull : 0ull);
-            atomicAdd(&g_k2b_stat[3], 1ull);
-            atomicAdd(&g_k2b_stat[4], (unsigned long long)(__popcll(bsub) / 16));
-            atomicAdd(&g_k2b_stat[5], (unsigned long long)segs_abv);
-          }
-        }
-#endif
         const bool pass = key <= Tk;  // at or above the query's k-th best tail score
         const uint64_t pm = __ballot(pass);
         if (pass) {
@@ -1162,11 +905,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K2B_WP
       }
     }
     wave_lds_sync();  // LDS reused by the next item
-#if K2B_STAT
-    if (!has_next) { stat_done(); break; }
-#else
     if (!has_next) break;
-#endif
     itx = nitx;
     item = nitem;
     item_sm = nitem_sm;
