@@ -330,6 +330,27 @@ class BM25Index:
                 "cm_bm25_build_dev")
         self.vocab = int(vocab)
 
+    def append(self, term_ids: np.ndarray, doc_off: np.ndarray, vocab: int):
+        """The documents become the rows after the existing ones, without a rebuild (cm_bm25_append):
+        the index then equals one built over all documents.  vocab >= the index's."""
+        t = _c(term_ids, np.int32)
+        o = _c(doc_off, np.int64)
+        n_new = int(o.shape[0] - 1)
+        L.check(L.fn["cm_bm25_append"](self._h, L.ptr(t), L.ptr(o), n_new, int(vocab)), "cm_bm25_append")
+        self._appended(n_new, vocab)
+
+    def append_dev(self, term_ids, doc_off, vocab: int):
+        assert term_ids.dtype == torch.int32 and doc_off.dtype == torch.int64
+        n_new = int(doc_off.numel() - 1)
+        L.check(L.fn["cm_bm25_append_dev"](self._h, L.ptr(term_ids), L.ptr(doc_off), n_new, int(term_ids.numel()),
+                                           int(vocab), _stream(self.device)), "cm_bm25_append_dev")
+        self._appended(n_new, vocab)
+
+    def _appended(self, n_new: int, vocab: int):
+        if n_new > 0:  # (an empty append changes nothing, the vocabulary included)
+            self.vocab = int(vocab)
+            self._ws = None  # the cached search workspace's size depends on the range count
+
     @property
     def num_docs(self) -> int:
         return int(L.fn["cm_bm25_num_docs"](self._h))

@@ -108,6 +108,29 @@ class RowMap:
         return [v[s] for s in range(n_shards)]
 
 
+def shard_spans(G: int, B: int, s: int, lo: int, hi: int) -> List[tuple]:
+    """The global rows of [lo, hi) that shard s of G holds at block size B, as (first, end) spans in
+    the shard's local order.  Every earlier block of a shard is full, so the spans of [n, m) extend
+    the shard's rows of [0, n) at its local end: spans(0, n) + spans(n, m) cover spans(0, m)."""
+    out = []
+    for b in range(s, -(-hi // B), G):
+        a, e = max(b * B, lo), min((b + 1) * B, hi)
+        if a < e:
+            out.append((a, e))
+    return out
+
+
+def _take_docs(term_ids, doc_off: np.ndarray, spans):
+    """(term ids, offsets from 0) of the documents in the spans, in order."""
+    if not spans:
+        return np.zeros(0, np.int32), np.zeros(1, np.int64)
+    tids = np.concatenate([np.asarray(term_ids[doc_off[lo]:doc_off[hi]], np.int32) for lo, hi in spans])
+    lens = np.concatenate([np.diff(doc_off[lo:hi + 1]) for lo, hi in spans])
+    off = np.zeros(lens.shape[0] + 1, np.int64)
+    np.cumsum(lens, out=off[1:])
+    return tids, off
+
+
 def _f32_key_np(d: np.ndarray, r: np.ndarray) -> np.ndarray:
     """(distance f32, row) -> int64 key ordering like (distance asc, row asc); rows < 0 last."""
     b = np.ascontiguousarray(d, np.float32).view(np.uint32).astype(np.int64)
@@ -410,6 +433,9 @@ class ShardedBM25Index(_Shards):
         self.idf = np.zeros(0, np.float64)
         self.n_live = self.sum_len = 0
         self.eps = 0.0
+        # every shard's own statistics, read after its build or append: set_stats then replaces them
+        # in the handle, and a shard that a later append gives no rows is not asked again
+        self._local = [None] * self.G
         self._st = None
 
     def close(self):
@@ -430,19 +456,55 @@ class ShardedBM25Index(_Shards):
         N = doc_off.shape[0] - 1
         B, G = self.map.B, self.G
         for s, sh in enumerate(self.shards):
-            spans = [(b * B, min((b + 1) * B, N)) for b in range(s, -(-N // B), G)]
-            if spans:
-                tids = np.concatenate([np.asarray(term_ids[doc_off[lo]:doc_off[hi]], np.int32) for lo, hi in spans])
-                lens = np.concatenate([np.diff(doc_off[lo:hi + 1]) for lo, hi in spans])
-                off = np.zeros(lens.shape[0] + 1, np.int64)
-                np.cumsum(lens, out=off[1:])
-                lv = None if live is None else np.concatenate([np.asarray(live[lo:hi]) for lo, hi in spans])
-            else:
-                tids, off, lv = np.zeros(0, np.int32), np.zeros(1, np.int64), None
+            spans = shard_spans(G, B, s, 0, N)
+            tids, off = _take_docs(term_ids, doc_off, spans)
+            lv = None if live is None or not spans else np.concatenate([np.asarray(live[lo:hi]) for lo, hi in spans])
             sh.build(tids, off, vocab, lv)
+            self._local[s] = sh.stats()
         self.vocab, self.ndocs = int(vocab), int(N)
         self._prepared = False
         self._install_global_stats()
+
+    def append(self, term_ids: np.ndarray, doc_off: np.ndarray, vocab: int):
+        """engine.BM25Index.append: the documents become global rows [ndocs, ndocs + n), each shard
+        appends the ones RowMap deals it (a shard without documents builds) and the global statistics
+        are installed again.  A shard that gets none keeps its smaller vocabulary: the terms beyond it
+        have no postings there, and its kernels take them for unknown terms."""
+        doc_off = np.asarray(doc_off, np.int64)
+        n_new = doc_off.shape[0] - 1
+        if n_new < 0 or vocab < self.vocab or (n_new and (doc_off[0] != 0 or (np.diff(doc_off) < 0).any())):
+            raise ValueError("bad arguments")
+        if n_new == 0:
+            return
+        tok = np.asarray(term_ids[:doc_off[-1]])
+        if tok.size and (tok.min() < 0 or tok.max() >= vocab):   # (checked here: no shard has changed yet)
+            raise ValueError("term id out of range")
+        N0 = self.ndocs
+        if N0 < 0:
+            raise ValueError("an append failed half way: build the index again")
+        try:
+            for s, sh in enumerate(self.shards):
+                spans = [(a - N0, e - N0) for a, e in shard_spans(self.G, self.map.B, s, N0, N0 + n_new)]
+                if spans:
+                    assert sh.num_docs == self.map.local_count(s, N0)
+                    sh.append(*_take_docs(term_ids, doc_off, spans), vocab)
+                    self._local[s] = sh.stats()
+        except Exception:
+            # (a tf above 65535, no memory) some shards have their rows and others do not: no document
+            # count describes the index until it is built again (BM25Store then rebuilds)
+            self.ndocs = -1
+            raise
+        self.vocab, self.ndocs = int(vocab), int(N0 + n_new)
+        self._prepared = False
+        self._install_global_stats()
+
+    def _on_vocab(self, a: np.ndarray, fill) -> np.ndarray:
+        """A shard's per-term array on the global vocabulary (see append)."""
+        if a.shape[0] == self.vocab:
+            return a
+        out = np.full(self.vocab, fill, a.dtype)
+        out[: a.shape[0]] = a
+        return out
 
     def _install_global_stats(self):
         V = self.vocab
@@ -453,9 +515,9 @@ class ShardedBM25Index(_Shards):
             if sh.num_docs == 0:
                 continue
             df, fk = sh.term_stats()
-            gdf += df.astype(np.int64)
-            gfk = np.minimum(gfk, self._global_keys(s, fk))
-            st = sh.stats()
+            gdf += self._on_vocab(df.astype(np.int64), 0)
+            gfk = np.minimum(gfk, self._on_vocab(self._global_keys(s, fk), _EMPTY))
+            st = self._local[s]
             n += st["n_live"]
             sl += st["sum_len"]
         self.n_live, self.sum_len = int(n), int(sl)
@@ -465,7 +527,7 @@ class ShardedBM25Index(_Shards):
         self.idf, self.eps = parallel.bm25_idf_table(gdf, gfk, n)
         for sh in self.shards:
             if sh.num_docs:
-                sh.set_stats(self.idf, n, sl, self.eps)
+                sh.set_stats(self.idf[: sh.vocab], n, sl, self.eps)
 
     def _global_keys(self, s: int, fk: np.ndarray) -> np.ndarray:
         """Shard s's first-occurrence keys (local row << 32 | position, ~0 absent) on global rows."""
@@ -483,8 +545,8 @@ class ShardedBM25Index(_Shards):
         for s, sh in enumerate(self.shards):
             if sh.num_docs:
                 df, fk = sh.term_stats()
-                gdf += df
-                gfk = np.minimum(gfk, self._global_keys(s, fk))
+                gdf += self._on_vocab(df, 0)
+                gfk = np.minimum(gfk, self._on_vocab(self._global_keys(s, fk), _EMPTY))
         return gdf, gfk
 
     def stats(self):
@@ -501,7 +563,7 @@ class ShardedBM25Index(_Shards):
             g = self.map.to_global(s, np.arange(c["dl"].shape[0], dtype=np.int64))
             dl[g] = c["dl"]
             cnt = np.diff(c["term_off"])
-            terms.append(np.repeat(np.arange(V, dtype=np.int64), cnt))
+            terms.append(np.repeat(np.arange(cnt.shape[0], dtype=np.int64), cnt))
             docs.append(self.map.to_global(s, c["post_doc"].astype(np.int64)))
             tfs.append(c["post_tf"])
             poss.append(c["post_pos"])
@@ -568,8 +630,8 @@ class ShardedBM25Index(_Shards):
                 continue
             with torch.cuda.device(self.devices[s]):
                 d, fk = sh.filter_term_stats_dev(parts_dev[s])
-            gdf += d.cpu().numpy()
-            gfk = np.minimum(gfk, self._global_keys(s, fk.cpu().numpy().view(np.uint64)))
+            gdf += self._on_vocab(d.cpu().numpy(), 0)
+            gfk = np.minimum(gfk, self._on_vocab(self._global_keys(s, fk.cpu().numpy().view(np.uint64)), _EMPTY))
         return parallel.bm25_idf_table(gdf, gfk, int(n_cand))[1]
 
     def _parts_dev(self, allow_bits):

@@ -9,7 +9,9 @@ duplicate query tokens counted twice (Q3), zero-score padding in insertion
 order (Q1), ZeroDivisionError on an all-empty vocabulary (Q7).
 
 The reference rebuilds BM25Okapi on every mutation and again per search; here
-mutations mark the device index dirty and the next search rebuilds it once.
+mutations mark the device index dirty and the next search rebuilds it once --
+or, after upserts of ids new to the store only, appends their rows to it
+(``engine.BM25Index.append``: no pass over the documents already indexed).
 
 Persistence: ``save`` writes the reference's JSONL catalog
 unchanged (bm25.py:220-231) plus a binary sidecar ``<index_file>.cm/`` -- the
@@ -154,6 +156,12 @@ class _BState:
         self.dirty = True
         self.meta_dirty = True
         self.csr: Optional[tuple] = None   # persisted (term_ids, doc_off) to build from
+        # the same once rows were appended behind it: the CSR of the first len(doc_off) - 1 rows, to
+        # build from before the others are appended (their records are never read for it)
+        self.prefix_csr: Optional[tuple] = None
+        # set while the device index lacks nothing but the rows from this one on (append-only upserts
+        # since it was current): the next search appends them instead of rebuilding
+        self.pending_row: Optional[int] = None
         self.version = 0                   # bumped by every change of the document set
         self.uid = next_uid()              # identity in device caches (never reused)
         self.sig = None                    # the JSONL (+ sidecar) signature it was loaded from / saved to
@@ -184,6 +192,7 @@ class _BState:
         st.id_list = list(self.id_list)
         st.vocab = dict(self.vocab)
         st.csr = self.csr
+        st.prefix_csr = self.prefix_csr   # (pending_row stays None: the clone builds from it, then appends)
         st.version = self.version
         return st
 
@@ -293,6 +302,8 @@ class BM25Store:
     _dirty = _proxy("dirty")
     _meta_dirty = _proxy("meta_dirty")
     _csr = _proxy("csr")
+    _prefix_csr = _proxy("prefix_csr")
+    _pending_row = _proxy("pending_row")
     _version = _proxy("version")
     _uid = _proxy("uid")
 
@@ -330,23 +341,34 @@ class BM25Store:
         entries exist but every token list is empty.  We check that and defer the device build."""
         self._id_list = list(self._entries.keys())
         self._version += 1
-        self._csr = None
+        self._csr = self._prefix_csr = None
+        self._pending_row = None
         if self._entries and all(len(e.tokens) == 0 for e in self._entries.values()):
             raise ZeroDivisionError("float division by zero")
         self._dirty = self._meta_dirty = True
 
-    def _ensure_index(self) -> None:
+    def _appended(self, new_ids: Sequence[str]) -> None:
+        """_rebuild after an upsert of ids new to the store only: they are the rows after the existing
+        ones, so the device index (or the persisted CSR it is yet to be built from) stays a valid
+        prefix and _ensure_index appends to it.  No earlier record is read."""
+        n0 = len(self._id_list)
+        self._id_list.extend(new_ids)
+        self._version += 1
+        if self._csr is not None:   # no longer the whole index
+            self._prefix_csr, self._csr = self._csr, None
+        if all(len(self._entries[i].tokens) == 0 for i in new_ids):   # bm25.py:145 over all entries
+            c, tokens = 0, 0
+            if self._prefix_csr is not None:   # the persisted rows' token count stands for their records
+                c, tokens = len(self._prefix_csr[1]) - 1, int(self._prefix_csr[1][-1])
+            if tokens == 0 and all(len(self._entries[i].tokens) == 0 for i in self._id_list[c:n0]):
+                raise ZeroDivisionError("float division by zero")
         if not self._dirty and self._index is not None:
-            return
-        if self._index is None:
-            self._index = multidev.new_bm25_index(device=self.device)
-        if self._csr is not None:  # opened from a sidecar: the persisted CSR is the index
-            term_ids, doc_off = self._csr
-            self._index.build(np.ascontiguousarray(term_ids), np.ascontiguousarray(doc_off),
-                              max(len(self._vocab), 1))
-            self._dirty = False
-            return
-        entries = [self._entries[i] for i in self._id_list]
+            self._pending_row = n0
+        self._dirty = True
+
+    def _rows_csr(self, r0: int):
+        """(term ids, offsets from 0) of rows [r0, n) from their entries."""
+        entries = [self._entries[i] for i in self._id_list[r0:]]
         for e in entries:
             if e.term_ids is None:
                 e.term_ids = self._term_ids(e.tokens)
@@ -354,7 +376,31 @@ class BM25Store:
         if entries:
             off[1:] = np.cumsum([e.term_ids.shape[0] for e in entries])
         flat = np.concatenate([e.term_ids for e in entries]) if off[-1] else np.zeros(0, np.int32)
-        self._index.build(flat, off, max(len(self._vocab), 1))
+        return flat, off
+
+    def _ensure_index(self) -> None:
+        if not self._dirty and self._index is not None:
+            return
+        if self._index is None:
+            self._index = multidev.new_bm25_index(device=self.device)
+        n = len(self._id_list)
+        have = self._pending_row   # rows the device index holds, when it is a prefix of the store
+        if have is None or self._index.num_docs != have:
+            csr = self._csr if self._csr is not None else self._prefix_csr
+            if csr is not None:  # opened from a sidecar: the persisted CSR is the index (of its rows)
+                term_ids, doc_off = csr
+                have = len(doc_off) - 1
+                # (the vocabulary may have grown with rows appended since; the CSR's ids are below it)
+                self._index.build(np.ascontiguousarray(term_ids), np.ascontiguousarray(doc_off),
+                                  max(len(self._vocab), 1))
+            else:
+                have = n
+                flat, off = self._rows_csr(0)     # (assigns the vocabulary's ids: before its size is read)
+                self._index.build(flat, off, max(len(self._vocab), 1))
+        if have < n:
+            flat, off = self._rows_csr(have)
+            self._index.append(flat, off, max(len(self._vocab), 1))
+        self._pending_row = None
         self._dirty = False
 
     def _ensure_meta(self) -> None:
@@ -390,7 +436,10 @@ class BM25Store:
                 appended.append((n0 + len(appended), meta))
             self._entries[doc_id] = _Entry(id=doc_id, text=text, tokens=toks, metadata=meta)
         meta_ok = not self._meta_dirty
-        self._rebuild()
+        if appended is not None:
+            self._appended(list(ids))
+        else:
+            self._rebuild()
         if meta_ok and appended is not None:   # the filter columns follow the appended rows
             for r, meta in appended:
                 self._meta.set(r, meta)

@@ -997,18 +997,28 @@ __global__ void __launch_bounds__(256) bm25_term_df_kernel(const int32_t *__rest
 }
 
 // ---------------- K7: device CSR build (radix sort by (term, doc)) ----------------
+// Document d of the batch is row doc_base + d of the index (an append: the rows after the existing
+// ones).  *bad: bit 0 a term id outside [0, vocab), bit 1 offsets that decrease or leave [0, ntokens].
 __global__ void bm25_token_keys_kernel(const int32_t *__restrict__ term_ids, const int64_t *__restrict__ doc_off,
-                                       int64_t ndocs, uint64_t *__restrict__ keys, uint32_t *__restrict__ pos,
+                                       int64_t ndocs, int64_t ntokens, int64_t doc_base, int32_t vocab,
+                                       uint64_t *__restrict__ keys, uint32_t *__restrict__ pos,
                                        int32_t *__restrict__ dl, int32_t *__restrict__ bad) {
   const int64_t d = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
   if (d >= ndocs) return;
   const int lane = threadIdx.x & 63;
   const int64_t b = doc_off[d], e = doc_off[d + 1];
+  if (b < 0 || e < b || e > ntokens) {  // (wave-uniform) nothing of this document is read or written
+    if (lane == 0) {
+      dl[d] = 0;
+      atomicOr(bad, 2);
+    }
+    return;
+  }
   if (lane == 0) dl[d] = (int32_t)(e - b);
   for (int64_t p = b + lane; p < e; p += 64) {
     const int32_t t = term_ids[p];
-    if (t < 0) atomicOr(bad, 1);
-    keys[p] = ((uint64_t)(uint32_t)t << 32) | (uint64_t)(uint32_t)d;
+    if (t < 0 || t >= vocab) atomicOr(bad, 1);
+    keys[p] = ((uint64_t)(uint32_t)t << 32) | (uint64_t)(uint32_t)(doc_base + d);
     pos[p] = (uint32_t)(p - b);
   }
 }
@@ -1124,6 +1134,7 @@ struct cm_bm25 {
   int64_t ndocs = 0, npost = 0;
   int32_t vocab = 0;
   int64_t n_live = 0, sum_len = 0;
+  int64_t own_live = 0, own_len = 0;  // this index's own counts (cm_bm25_set_stats replaces the two above)
   double avgdl = 0.0, eps = 0.0;
   bool empty_vocab = false;  // live docs exist but no tokens (ZeroDivisionError on search)
   DevBuf term_off, post_doc, post_tf, post_pos, dl, live, idf;
@@ -1609,7 +1620,146 @@ int filtered_eps(cm_bm25 *h, const uint32_t *allow_dev, int64_t n_cand, double *
   return CM_OK;
 }
 
+struct TmpBuf : DevBuf {  // scratch: freed when the call returns, on every path
+  TmpBuf() = default;
+  TmpBuf(const TmpBuf &) = delete;
+  TmpBuf &operator=(const TmpBuf &) = delete;
+  ~TmpBuf() { release(); }
+};
+
+// The filtered searches' table L[x] = log(x + 0.5) for x <= n: the entries beyond the current
+// table are computed (glibc, as bm25_idf) and uploaded, the current ones kept.
+int bm25_grow_logtab(cm_bm25 *h, int64_t n) {
+  if (n <= h->log_n) return CM_OK;
+  const int64_t have = h->log_n + 1;
+  std::vector<double> L((size_t)(n + 1 - have));
+  for (int64_t x = have; x <= n; ++x) L[(size_t)(x - have)] = std::log((double)x + 0.5);
+  TmpBuf grown;
+  int rc = grown.ensure((size_t)(n + 1) * 8);
+  if (rc) return rc;
+  if (have)
+    CM_HIP(hipMemcpyAsync(grown.ptr, h->logtab.ptr, (size_t)have * 8, hipMemcpyDeviceToDevice, h->stream));
+  CM_HIP(hipMemcpyAsync(grown.as<double>() + have, L.data(), L.size() * 8, hipMemcpyHostToDevice, h->stream));
+  CM_HIP(hipStreamSynchronize(h->stream));
+  std::swap(h->logtab.ptr, grown.ptr);  // (grown frees the old table)
+  std::swap(h->logtab.bytes, grown.bytes);
+  h->log_n = n;
+  return CM_OK;
+}
+
+// K7, first half (cm_bm25_build_dev and cm_bm25_append_dev): the CSR postings of ndocs documents'
+// tokens (device arrays) -- (term, row) keys, radix sort, run-length encode, one posting per run --
+// into the caller's buffers: term_off[vocab + 1], post_*[*npost], dl[ndocs].  Document d is row
+// doc_base + d.  Synchronises `st`; a bad term id or offset (CM_EINVAL) is reported before the
+// postings are written, a tf above 65535 (CM_EUNSUPPORTED) after.
+int bm25_csr_from_tokens(hipStream_t st, const int32_t *term_ids_dev, const int64_t *doc_off_dev, int64_t ndocs,
+                         int64_t ntokens, int32_t vocab, int64_t doc_base, DevBuf &term_off, DevBuf &post_doc,
+                         DevBuf &post_tf, DevBuf &post_pos, DevBuf &dl, int64_t *npost) {
+  int rc;
+  TmpBuf keys_a, keys_b, pos_a, pos_b, runstart, nruns_d, flags, cub_tmp;  // keys in/out (u64), pos in/out (u32)
+  const size_t nt = (size_t)std::max<int64_t>(ntokens, 1);
+  if ((rc = keys_a.ensure(nt * 8)) || (rc = keys_b.ensure(nt * 8)) || (rc = pos_a.ensure(nt * 4)) ||
+      (rc = pos_b.ensure(nt * 4)) || (rc = flags.ensure(16)) || (rc = nruns_d.ensure(8)) ||
+      (rc = dl.ensure((size_t)ndocs * 4)))
+    return rc;
+  CM_HIP(hipMemsetAsync(flags.ptr, 0, 16, st));
+  hipLaunchKernelGGL(bm25_token_keys_kernel, dim3((unsigned)ceil_div(ndocs, 4)), dim3(256), 0, st, term_ids_dev,
+                     doc_off_dev, ndocs, ntokens, doc_base, vocab, keys_a.as<uint64_t>(), pos_a.as<uint32_t>(),
+                     dl.as<int32_t>(), flags.as<int32_t>());
+  CM_HIP(hipGetLastError());
+  int tbits = 1;
+  while ((1ll << tbits) < (int64_t)vocab) ++tbits;
+  hipcub::DoubleBuffer<uint64_t> kbuf(keys_a.as<uint64_t>(), keys_b.as<uint64_t>());
+  hipcub::DoubleBuffer<uint32_t> vbuf(pos_a.as<uint32_t>(), pos_b.as<uint32_t>());
+  size_t tmp_bytes = 0;
+  CM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, kbuf, vbuf, ntokens, 0, 32 + tbits, st));
+  if ((rc = cub_tmp.ensure(tmp_bytes))) return rc;
+  CM_HIP(hipcub::DeviceRadixSort::SortPairs(cub_tmp.ptr, tmp_bytes, kbuf, vbuf, ntokens, 0, 32 + tbits, st));
+  uint64_t *sk = kbuf.Current();
+  uint32_t *sp = vbuf.Current();
+  // runs of equal (term, doc): unique keys + counts; reuse the free buffers
+  uint64_t *uk = kbuf.Alternate();
+  int32_t *cnt = reinterpret_cast<int32_t *>(vbuf.Alternate());
+  size_t tmp2 = 0;
+  CM_HIP(hipcub::DeviceRunLengthEncode::Encode(nullptr, tmp2, sk, uk, cnt, nruns_d.as<int64_t>(), ntokens, st));
+  if (tmp2 > cub_tmp.bytes) {
+    cub_tmp.release();
+    if ((rc = cub_tmp.ensure(tmp2))) return rc;
+  }
+  CM_HIP(hipcub::DeviceRunLengthEncode::Encode(cub_tmp.ptr, tmp2, sk, uk, cnt, nruns_d.as<int64_t>(), ntokens, st));
+  int64_t nruns = 0;
+  int32_t hflags[2] = {0, 0};
+  CM_HIP(hipMemcpyAsync(&nruns, nruns_d.ptr, 8, hipMemcpyDeviceToHost, st));
+  CM_HIP(hipMemcpyAsync(hflags, flags.ptr, 8, hipMemcpyDeviceToHost, st));
+  CM_HIP(hipStreamSynchronize(st));
+  if (hflags[0] & 1) CM_FAIL(CM_EINVAL, "term id out of range");
+  if (hflags[0] & 2) CM_FAIL(CM_EINVAL, "doc_off must be non-decreasing within [0, ntokens]");
+  if ((rc = runstart.ensure((size_t)std::max<int64_t>(nruns, 1) * 8))) return rc;
+  // run_start = exclusive scan of counts (as int64)
+  {
+    size_t tmp3 = 0;
+    auto in = hipcub::TransformInputIterator<int64_t, hipcub::CastOp<int64_t>, int32_t *>(cnt, hipcub::CastOp<int64_t>());
+    CM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp3, in, runstart.as<int64_t>(), nruns, st));
+    if (tmp3 > cub_tmp.bytes) {
+      cub_tmp.release();
+      if ((rc = cub_tmp.ensure(tmp3))) return rc;
+    }
+    CM_HIP(hipcub::DeviceScan::ExclusiveSum(cub_tmp.ptr, tmp3, in, runstart.as<int64_t>(), nruns, st));
+  }
+  if ((rc = post_doc.ensure((size_t)std::max<int64_t>(nruns, 1) * 4)) ||
+      (rc = post_tf.ensure((size_t)std::max<int64_t>(nruns, 1) * 2)) ||
+      (rc = post_pos.ensure((size_t)std::max<int64_t>(nruns, 1) * 4)) ||
+      (rc = term_off.ensure(((size_t)vocab + 1) * 8)))
+    return rc;
+  if (nruns == 0) CM_HIP(hipMemsetAsync(term_off.ptr, 0, ((size_t)vocab + 1) * 8, st));
+  hipLaunchKernelGGL(bm25_postings_from_runs_kernel, dim3((unsigned)ceil_div(std::max<int64_t>(nruns, 1), 256)),
+                     dim3(256), 0, st, uk, cnt, runstart.as<int64_t>(), sp, nruns, post_doc.as<int32_t>(),
+                     post_tf.as<uint16_t>(), post_pos.as<uint32_t>(), term_off.as<int64_t>(), vocab,
+                     flags.as<int32_t>() + 1);
+  CM_HIP(hipGetLastError());
+  CM_HIP(hipMemcpyAsync(hflags, flags.ptr, 8, hipMemcpyDeviceToHost, st));
+  CM_HIP(hipStreamSynchronize(st));
+  if (hflags[1]) CM_FAIL(CM_EUNSUPPORTED, "term frequency > 65535 in one chunk");
+  *npost = nruns;
+  return CM_OK;
+}
+
+// K7, second half: what a build derives from the handle's CSR arrays and counts -- df from
+// term_off, the terms' first-occurrence order (first_key_kernel + host sort), the idf table and
+// the head tiles.  The arrays were written on `st`.
+int bm25_finish_build(cm_bm25 *h, hipStream_t st) {
+  const int32_t vocab = h->vocab;
+  int rc;
+  TmpBuf firstk;
+  if ((rc = firstk.ensure((size_t)std::max(vocab, 1) * 8))) return rc;
+  if (vocab > 0) {
+    hipLaunchKernelGGL(first_key_kernel, dim3((unsigned)ceil_div(vocab, 256)), dim3(256), 0, st,
+                       h->term_off.as<int64_t>(), h->post_doc.as<int32_t>(), h->post_pos.as<uint32_t>(), vocab,
+                       firstk.as<uint64_t>());
+    CM_HIP(hipGetLastError());
+  }
+  std::vector<int32_t> df((size_t)vocab);
+  std::vector<int64_t> toff_h((size_t)vocab + 1);
+  std::vector<uint64_t> fk((size_t)vocab);
+  CM_HIP(hipMemcpyAsync(toff_h.data(), h->term_off.ptr, ((size_t)vocab + 1) * 8, hipMemcpyDeviceToHost, st));
+  if (vocab > 0) CM_HIP(hipMemcpyAsync(fk.data(), firstk.ptr, (size_t)vocab * 8, hipMemcpyDeviceToHost, st));
+  CM_HIP(hipStreamSynchronize(st));
+  for (int32_t t = 0; t < vocab; ++t) df[t] = (int32_t)(toff_h[t + 1] - toff_h[t]);
+  std::vector<int32_t> order;
+  order.reserve((size_t)vocab);
+  for (int32_t t = 0; t < vocab; ++t)
+    if (df[t] > 0) order.push_back(t);
+  std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return fk[a] < fk[b]; });
+  if ((rc = compute_idf_table(h, df, order))) return rc;
+  if ((rc = build_head_tiles(h, df))) return rc;
+  CM_HIP(hipStreamSynchronize(h->stream));
+  if (h->empty_vocab) CM_FAIL(CM_EZERODIV, "float division by zero (every live document has an empty token list)");
+  return CM_OK;
+}
+
 }  // namespace
+
+#include "cm_bm25_append.inc"
 
 extern "C" {
 
@@ -1738,8 +1888,8 @@ int cm_bm25_build(cm_bm25 *h, const int32_t *term_ids, const int64_t *doc_off, i
   h->ndocs = ndocs;
   h->npost = npost;
   h->vocab = vocab;
-  h->n_live = n_live;
-  h->sum_len = sum_len;
+  h->n_live = h->own_live = n_live;
+  h->sum_len = h->own_len = sum_len;
   if ((rc = compute_idf_table(h, df, order))) return rc;
   if ((rc = build_head_tiles(h, df))) return rc;
   CM_HIP(hipStreamSynchronize(h->stream));
@@ -1755,130 +1905,21 @@ int cm_bm25_build_dev(cm_bm25 *h, const int32_t *term_ids_dev, const int64_t *do
   DeviceGuard dg(h->dev);
   hipStream_t st = (hipStream_t)stream;  // NULL = the null stream (torch default)
   int rc;
-  // scratch: keys in/out (u64), pos in/out (u32), flags
-  DevBuf keys_a, keys_b, pos_a, pos_b, ukeys, counts, runstart, nruns_d, flags, df_d, cub_tmp, firstk;
-  auto cleanup = [&]() {
-    for (DevBuf *b : {&keys_a, &keys_b, &pos_a, &pos_b, &ukeys, &counts, &runstart, &nruns_d, &flags, &df_d, &cub_tmp,
-                      &firstk})
-      b->release();
-  };
-  const size_t nt = (size_t)std::max<int64_t>(ntokens, 1);
-  if ((rc = keys_a.ensure(nt * 8)) || (rc = keys_b.ensure(nt * 8)) || (rc = pos_a.ensure(nt * 4)) ||
-      (rc = pos_b.ensure(nt * 4)) || (rc = flags.ensure(16)) || (rc = h->dl.ensure((size_t)ndocs * 4))) {
-    cleanup();
+  int64_t npost = 0;
+  if ((rc = bm25_csr_from_tokens(st, term_ids_dev, doc_off_dev, ndocs, ntokens, vocab, 0, h->term_off, h->post_doc,
+                                 h->post_tf, h->post_pos, h->dl, &npost)))
     return rc;
-  }
-  CM_HIP(hipMemsetAsync(flags.ptr, 0, 16, st));
-  hipLaunchKernelGGL(bm25_token_keys_kernel, dim3((unsigned)ceil_div(ndocs, 4)), dim3(256), 0, st, term_ids_dev,
-                     doc_off_dev, ndocs, keys_a.as<uint64_t>(), pos_a.as<uint32_t>(), h->dl.as<int32_t>(),
-                     flags.as<int32_t>());
-  CM_HIP(hipGetLastError());
-  int tbits = 1;
-  while ((1ll << tbits) < (int64_t)vocab) ++tbits;
-  hipcub::DoubleBuffer<uint64_t> kbuf(keys_a.as<uint64_t>(), keys_b.as<uint64_t>());
-  hipcub::DoubleBuffer<uint32_t> vbuf(pos_a.as<uint32_t>(), pos_b.as<uint32_t>());
-  size_t tmp_bytes = 0;
-  CM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, kbuf, vbuf, ntokens, 0, 32 + tbits, st));
-  if ((rc = cub_tmp.ensure(tmp_bytes))) {
-    cleanup();
-    return rc;
-  }
-  CM_HIP(hipcub::DeviceRadixSort::SortPairs(cub_tmp.ptr, tmp_bytes, kbuf, vbuf, ntokens, 0, 32 + tbits, st));
-  uint64_t *sk = kbuf.Current();
-  uint32_t *sp = vbuf.Current();
-  // runs of equal (term, doc): unique keys + counts; reuse the free buffers
-  uint64_t *uk = kbuf.Alternate();
-  int32_t *cnt = reinterpret_cast<int32_t *>(vbuf.Alternate());
-  if ((rc = nruns_d.ensure(8))) {
-    cleanup();
-    return rc;
-  }
-  size_t tmp2 = 0;
-  CM_HIP(hipcub::DeviceRunLengthEncode::Encode(nullptr, tmp2, sk, uk, cnt, nruns_d.as<int64_t>(), ntokens, st));
-  if (tmp2 > cub_tmp.bytes) {
-    cub_tmp.release();
-    if ((rc = cub_tmp.ensure(tmp2))) {
-      cleanup();
-      return rc;
-    }
-  }
-  CM_HIP(hipcub::DeviceRunLengthEncode::Encode(cub_tmp.ptr, tmp2, sk, uk, cnt, nruns_d.as<int64_t>(), ntokens, st));
-  int64_t nruns = 0;
-  int32_t hflags[2] = {0, 0};
-  CM_HIP(hipMemcpyAsync(&nruns, nruns_d.ptr, 8, hipMemcpyDeviceToHost, st));
-  CM_HIP(hipMemcpyAsync(hflags, flags.ptr, 8, hipMemcpyDeviceToHost, st));
-  CM_HIP(hipStreamSynchronize(st));
-  if (hflags[0]) {
-    cleanup();
-    CM_FAIL(CM_EINVAL, "term id out of range");
-  }
-  if ((rc = runstart.ensure((size_t)std::max<int64_t>(nruns, 1) * 8))) {
-    cleanup();
-    return rc;
-  }
-  // run_start = exclusive scan of counts (as int64)
-  {
-    size_t tmp3 = 0;
-    auto in = hipcub::TransformInputIterator<int64_t, hipcub::CastOp<int64_t>, int32_t *>(cnt, hipcub::CastOp<int64_t>());
-    CM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp3, in, runstart.as<int64_t>(), nruns, st));
-    if (tmp3 > cub_tmp.bytes) {
-      cub_tmp.release();
-      if ((rc = cub_tmp.ensure(tmp3))) {
-        cleanup();
-        return rc;
-      }
-    }
-    CM_HIP(hipcub::DeviceScan::ExclusiveSum(cub_tmp.ptr, tmp3, in, runstart.as<int64_t>(), nruns, st));
-  }
-  if ((rc = h->post_doc.ensure((size_t)std::max<int64_t>(nruns, 1) * 4)) ||
-      (rc = h->post_tf.ensure((size_t)std::max<int64_t>(nruns, 1) * 2)) ||
-      (rc = h->post_pos.ensure((size_t)std::max<int64_t>(nruns, 1) * 4)) ||
-      (rc = h->term_off.ensure(((size_t)vocab + 1) * 8))) {
-    cleanup();
-    return rc;
-  }
-  if (nruns == 0) CM_HIP(hipMemsetAsync(h->term_off.ptr, 0, ((size_t)vocab + 1) * 8, st));
-  hipLaunchKernelGGL(bm25_postings_from_runs_kernel, dim3((unsigned)ceil_div(std::max<int64_t>(nruns, 1), 256)),
-                     dim3(256), 0, st, uk, cnt, runstart.as<int64_t>(), sp, nruns, h->post_doc.as<int32_t>(),
-                     h->post_tf.as<uint16_t>(), h->post_pos.as<uint32_t>(), h->term_off.as<int64_t>(), vocab,
-                     flags.as<int32_t>() + 1);
-  CM_HIP(hipGetLastError());
   const int64_t nw = std::max<int64_t>(1, ceil_div(ndocs, 32));
-  if ((rc = h->live.ensure((size_t)nw * 4)) || (rc = firstk.ensure((size_t)vocab * 8))) {
-    cleanup();
-    return rc;
-  }
+  if ((rc = h->live.ensure((size_t)nw * 4))) return rc;
   hipLaunchKernelGGL(set_all_bits_kernel, dim3((unsigned)ceil_div(nw, 256)), dim3(256), 0, st, h->live.as<uint32_t>(),
                      ndocs);
-  hipLaunchKernelGGL(first_key_kernel, dim3((unsigned)ceil_div(vocab, 256)), dim3(256), 0, st,
-                     h->term_off.as<int64_t>(), h->post_doc.as<int32_t>(), h->post_pos.as<uint32_t>(), vocab,
-                     firstk.as<uint64_t>());
   CM_HIP(hipGetLastError());
-  std::vector<int32_t> df((size_t)vocab);
-  std::vector<int64_t> toff_h((size_t)vocab + 1);
-  std::vector<uint64_t> fk((size_t)vocab);
-  CM_HIP(hipMemcpyAsync(toff_h.data(), h->term_off.ptr, ((size_t)vocab + 1) * 8, hipMemcpyDeviceToHost, st));
-  CM_HIP(hipMemcpyAsync(fk.data(), firstk.ptr, (size_t)vocab * 8, hipMemcpyDeviceToHost, st));
-  CM_HIP(hipMemcpyAsync(hflags, flags.ptr, 8, hipMemcpyDeviceToHost, st));
-  CM_HIP(hipStreamSynchronize(st));
-  cleanup();
-  for (int32_t t = 0; t < vocab; ++t) df[t] = (int32_t)(toff_h[t + 1] - toff_h[t]);
-  if (hflags[1]) CM_FAIL(CM_EUNSUPPORTED, "term frequency > 65535 in one chunk");
-  std::vector<int32_t> order;
-  order.reserve((size_t)vocab);
-  for (int32_t t = 0; t < vocab; ++t)
-    if (df[t] > 0) order.push_back(t);
-  std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return fk[a] < fk[b]; });
   h->ndocs = ndocs;
-  h->npost = nruns;
+  h->npost = npost;
   h->vocab = vocab;
-  h->n_live = ndocs;
-  h->sum_len = ntokens;
-  if ((rc = compute_idf_table(h, df, order))) return rc;
-  if ((rc = build_head_tiles(h, df))) return rc;
-  CM_HIP(hipStreamSynchronize(h->stream));
-  if (h->empty_vocab) CM_FAIL(CM_EZERODIV, "float division by zero (every live document has an empty token list)");
-  return CM_OK;
+  h->n_live = h->own_live = ndocs;
+  h->sum_len = h->own_len = ntokens;
+  return bm25_finish_build(h, st);
 }
 
 int cm_bm25_term_stats(cm_bm25 *h, int32_t *df_out, uint64_t *first_out) {
@@ -2249,17 +2290,8 @@ int cm_bm25_search_idf(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_off,
 int cm_bm25_prepare_filtered(cm_bm25 *h, int64_t max_docs) {
   if (!h) CM_FAIL(CM_EINVAL, "null handle");
   if (max_docs < 0 || max_docs >= (int64_t)1 << 40) CM_FAIL(CM_EINVAL, "bad max_docs");
-  const int64_t n = std::max(max_docs, h->ndocs);
-  if (n <= h->log_n) return CM_OK;
   DeviceGuard dg(h->dev);
-  std::vector<double> L((size_t)n + 1);
-  for (int64_t x = 0; x <= n; ++x) L[(size_t)x] = std::log((double)x + 0.5);  // glibc, as bm25_idf
-  int rc = h->logtab.ensure(L.size() * 8);
-  if (rc) return rc;
-  CM_HIP(hipMemcpyAsync(h->logtab.ptr, L.data(), L.size() * 8, hipMemcpyHostToDevice, h->stream));
-  CM_HIP(hipStreamSynchronize(h->stream));
-  h->log_n = n;
-  return CM_OK;
+  return bm25_grow_logtab(h, std::max(max_docs, h->ndocs));
 }
 
 int cm_bm25_filter_stats_dev(cm_bm25 *h, const uint32_t *allow_dev, const int32_t *q_terms_dev, int32_t n_terms,

@@ -219,6 +219,22 @@ int cm_bm25_build(cm_bm25 *h, const int32_t *term_ids, const int64_t *doc_off, i
 /* same from device arrays (K7: device CSR build by radix sort). */
 int cm_bm25_build_dev(cm_bm25 *h, const int32_t *term_ids_dev, const int64_t *doc_off_dev, int64_t ndocs,
                       int64_t ntokens, int32_t vocab, void *stream);
+/* BM25Store.upsert_many for ids new to the store (rag/retrieval/bm25.py:147-166): the n_new
+ * documents (doc_off[n_new + 1] from 0, term ids in [0, vocab), vocab >= the index's) become
+ * rows [ndocs, ndocs + n_new), all live, without a rebuild: their postings are built on the
+ * device and merged behind each term's existing ones.  Afterwards the handle equals one that
+ * cm_bm25_build made over all documents, old then new, with the old documents' live bytes:
+ * exports, statistics and every search, bit for bit.  Local statistics replace any installed
+ * with cm_bm25_set_stats; a prepared filter table (cm_bm25_prepare_filtered) grows with the
+ * document count.  An index without documents gets the build; n_new == 0 changes nothing.
+ * Errors (as cm_bm25_build's; vocab below the index's: CM_EINVAL) leave the handle as it was,
+ * except CM_EZERODIV, which cm_bm25_build also reports after the fact.  Peak device memory:
+ * old + new postings.  Host semantics as cm_bm25_build (only the new documents are uploaded);
+ * _dev as cm_bm25_build_dev: synchronises, not capturable, no search on the handle meanwhile.
+ * With cm_bm25_timing on, the merge kernel's time is the next cm_bm25_timing_drain entry.     */
+int cm_bm25_append(cm_bm25 *h, const int32_t *term_ids, const int64_t *doc_off, int64_t n_new, int32_t vocab);
+int cm_bm25_append_dev(cm_bm25 *h, const int32_t *term_ids_dev, const int64_t *doc_off_dev, int64_t n_new,
+                       int64_t ntokens, int32_t vocab, void *stream);
 int64_t cm_bm25_num_docs(cm_bm25 *h);
 int64_t cm_bm25_num_postings(cm_bm25 *h);
 /* unfiltered corpus statistics: live docs, total length, avgdl, eps. */
