@@ -351,6 +351,22 @@ class BM25Index:
             self.vocab = int(vocab)
             self._ws = None  # the cached search workspace's size depends on the range count
 
+    def remove(self, rows):
+        """Remove the documents at these rows (any order, duplicates allowed) and renumber the
+        survivors in order, without a rebuild (cm_bm25_remove): the index then equals one built
+        over the surviving documents."""
+        r = _c(np.asarray(rows).reshape(-1), np.int64)
+        L.check(L.fn["cm_bm25_remove"](self._h, L.ptr(r), int(r.shape[0])), "cm_bm25_remove")
+        self._ws = None  # the cached search workspace's size depends on the range count
+
+    def remove_dev(self, bits):
+        """The same from a device bitmap: int32/uint32 tensor of ceil(num_docs / 32) words, bit r of
+        word r // 32 set = remove row r (on the current stream)."""
+        assert bits.is_cuda and bits.element_size() == 4 and not bits.dtype.is_floating_point and bits.is_contiguous()
+        assert bits.numel() == (self.num_docs + 31) // 32
+        L.check(L.fn["cm_bm25_remove_dev"](self._h, L.ptr(bits), _stream(self.device)), "cm_bm25_remove_dev")
+        self._ws = None
+
     @property
     def num_docs(self) -> int:
         return int(L.fn["cm_bm25_num_docs"](self._h))

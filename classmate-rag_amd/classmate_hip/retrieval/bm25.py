@@ -11,7 +11,13 @@ order (Q1), ZeroDivisionError on an all-empty vocabulary (Q7).
 The reference rebuilds BM25Okapi on every mutation and again per search; here
 mutations mark the device index dirty and the next search rebuilds it once --
 or, after upserts of ids new to the store only, appends their rows to it
-(``engine.BM25Index.append``: no pass over the documents already indexed).
+(``engine.BM25Index.append``: no pass over the documents already indexed), and
+after deletes drops their rows from it (``engine.BM25Index.remove``: a device-side
+compaction of the postings; no token list, term id or record of a document that
+stays is read).  Between two searches any sequence of deletes and new-id upserts
+is recorded (``_BState.pending_drop`` / ``pending_row``) and applied as at most one
+``remove`` followed by at most one ``append``.  A replace in place keeps the
+replaced document's row, which neither expresses, and still rebuilds.
 
 Persistence: ``save`` writes the reference's JSONL catalog
 unchanged (bm25.py:220-231) plus a binary sidecar ``<index_file>.cm/`` -- the
@@ -162,6 +168,13 @@ class _BState:
         # set while the device index lacks nothing but the rows from this one on (append-only upserts
         # since it was current): the next search appends them instead of rebuilding
         self.pending_row: Optional[int] = None
+        # device rows (ascending, unique) of documents deleted since the index was current: the next
+        # search drops them first (engine.BM25Index.remove); pending_row counts in the numbering
+        # after that drop.  Together: "drop these device rows, then append the rows from pending_row on"
+        self.pending_drop: Optional[np.ndarray] = None
+        # tokens of all documents in the store, kept in step by deletes and appends once a delete on
+        # the device index has seeded it (None: not known); decides bm25.py:145 without the catalog
+        self.ntokens: Optional[int] = None
         self.version = 0                   # bumped by every change of the document set
         self.uid = next_uid()              # identity in device caches (never reused)
         self.sig = None                    # the JSONL (+ sidecar) signature it was loaded from / saved to
@@ -256,6 +269,28 @@ def _load_meta_snapshot(side: Path, n: int, cat: "_Catalog", ids: List[str]) -> 
         return None
 
 
+def _compacted_meta(meta: MetaIndex, keep: np.ndarray, cat, ids: List[str]) -> MetaIndex:
+    """MetaIndex.compacted(keep) that leaves a sidecar-opened store's unparsed metadata unparsed:
+    the rows' raw slots move (None where a record is not parsed yet) and the result's ``metas``
+    parse on demand against the new id list."""
+    lazy = meta.metas if isinstance(meta.metas, _CatalogMetas) else None
+    if lazy is None:
+        return meta.compacted(keep)
+    meta.metas = list(lazy)                    # (list's own iterator: raw slots, nothing parsed)
+    try:
+        m = meta.compacted(keep)
+    finally:
+        meta.metas = lazy
+    done = np.ones(len(m.metas), np.uint8)
+    old = keep < len(lazy.done)                # (rows behind the opened ones were set, not parsed)
+    done[old] = np.frombuffer(lazy.done, np.uint8)[keep[old]]
+    out = _CatalogMetas(len(m.metas), cat, ids)
+    list.__setitem__(out, slice(None), m.metas)
+    out.done = bytearray(done.tobytes())
+    m.metas = out
+    return m
+
+
 _REGISTRY: "OrderedDict[tuple, _BState]" = OrderedDict()
 _REGISTRY_MAX = 8
 _REG_LOCK = threading.Lock()
@@ -304,6 +339,8 @@ class BM25Store:
     _csr = _proxy("csr")
     _prefix_csr = _proxy("prefix_csr")
     _pending_row = _proxy("pending_row")
+    _pending_drop = _proxy("pending_drop")
+    _ntokens = _proxy("ntokens")
     _version = _proxy("version")
     _uid = _proxy("uid")
 
@@ -342,7 +379,7 @@ class BM25Store:
         self._id_list = list(self._entries.keys())
         self._version += 1
         self._csr = self._prefix_csr = None
-        self._pending_row = None
+        self._pending_row = self._pending_drop = self._ntokens = None
         if self._entries and all(len(e.tokens) == 0 for e in self._entries.values()):
             raise ZeroDivisionError("float division by zero")
         self._dirty = self._meta_dirty = True
@@ -362,9 +399,52 @@ class BM25Store:
                 c, tokens = len(self._prefix_csr[1]) - 1, int(self._prefix_csr[1][-1])
             if tokens == 0 and all(len(self._entries[i].tokens) == 0 for i in self._id_list[c:n0]):
                 raise ZeroDivisionError("float division by zero")
-        if not self._dirty and self._index is not None:
+        if self._ntokens is not None:
+            self._ntokens += sum(len(self._entries[i].tokens) for i in new_ids)
+        # the index is current, or lacks only rows to drop: from now on it also lacks the rows from n0 on
+        if (self._index is not None and self._pending_row is None
+                and (not self._dirty or self._pending_drop is not None)):
             self._pending_row = n0
         self._dirty = True
+
+    def _removable(self) -> bool:
+        """delete_many may leave the device index in place: there is one, it is current or lacks only
+        what this mechanism has pending (rows to drop, rows to append), and it can drop rows."""
+        return (self._index is not None and hasattr(self._index, "remove")
+                and (not self._dirty or self._pending_row is not None or self._pending_drop is not None))
+
+    def _removed(self, popped: Sequence[tuple]) -> None:
+        """_rebuild after a delete, on an index that _removable(): the popped documents' rows are
+        found in one pass over the id list and recorded for _ensure_index -- device rows to drop, or
+        rows taken out of the tail yet to be appended.  No record, token list or term id of a
+        document that stays is read.  ``popped``: (id, its _Entry) of the popped documents."""
+        gone = dict(popped)
+        old_ids = self._id_list
+        n0 = len(old_ids)
+        if self._ntokens is None:   # seed: the index's own count, plus the tail it does not hold yet
+            have = n0 if self._pending_row is None else self._pending_row
+            self._ntokens = int(self._index.stats()["sum_len"]) + sum(
+                len((gone.get(i) or self._entries[i]).tokens) for i in old_ids[have:])
+        self._ntokens -= sum(len(e.tokens) for e in gone.values())
+        rows = np.fromiter((r for r, i in enumerate(old_ids) if i in gone), np.int64)
+        self._id_list = [i for i in old_ids if i not in gone]
+        self._version += 1
+        self._csr = self._prefix_csr = None
+        have = n0 if self._pending_row is None else self._pending_row
+        held = rows[rows < have]               # rows the device holds, in the numbering after the pending drop
+        if held.shape[0]:
+            drop = self._pending_drop if self._pending_drop is not None else np.zeros(0, np.int64)
+            # device row of store row i: i + k, k = the pending drops at or below it (drop[j] - j <= i)
+            k = np.searchsorted(drop - np.arange(drop.shape[0]), held, side="right")
+            self._pending_drop = np.union1d(drop, held + k)
+            if self._pending_row is not None:
+                self._pending_row -= int(held.shape[0])
+            self._dirty = True
+        if not self._meta_dirty and rows.shape[0]:   # the filter columns follow (as GpuVectorStore.compact)
+            keep = np.setdiff1d(np.arange(n0, dtype=np.int64), rows, assume_unique=True)
+            self._meta = _compacted_meta(self._meta, keep, self._entries, self._id_list)
+        if self._ntokens == 0:                 # bm25.py:145: documents remain, every token list is empty
+            raise ZeroDivisionError("float division by zero")
 
     def _rows_csr(self, r0: int):
         """(term ids, offsets from 0) of rows [r0, n) from their entries."""
@@ -384,7 +464,15 @@ class BM25Store:
         if self._index is None:
             self._index = multidev.new_bm25_index(device=self.device)
         n = len(self._id_list)
-        have = self._pending_row   # rows the device index holds, when it is a prefix of the store
+        drop = self._pending_drop  # device rows to drop first, when deletes are pending
+        have = self._pending_row   # rows the device index holds (after that drop), when it is a prefix of the store
+        if drop is not None:
+            if have is None:
+                have = n
+            if hasattr(self._index, "remove") and self._index.num_docs == have + drop.shape[0]:
+                self._index.remove(drop)
+            else:
+                have = None
         if have is None or self._index.num_docs != have:
             csr = self._csr if self._csr is not None else self._prefix_csr
             if csr is not None:  # opened from a sidecar: the persisted CSR is the index (of its rows)
@@ -400,7 +488,7 @@ class BM25Store:
         if have < n:
             flat, off = self._rows_csr(have)
             self._index.append(flat, off, max(len(self._vocab), 1))
-        self._pending_row = None
+        self._pending_row = self._pending_drop = None
         self._dirty = False
 
     def _ensure_meta(self) -> None:
@@ -449,9 +537,16 @@ class BM25Store:
     def delete_many(self, ids: Sequence[str]) -> None:
         self._mutating()
         self._st.append_only = False
+        removable = self._removable()
+        popped = []
         for doc_id in ids:
-            self._entries.pop(doc_id, None)
-        self._rebuild()
+            e = self._entries.pop(doc_id, None)
+            if e is not None:
+                popped.append((doc_id, e))
+        if removable and self._entries:
+            self._removed(popped)
+        else:
+            self._rebuild()
 
     # ---------- query ----------
     def _query_ids(self, query: str) -> List[int]:

@@ -1627,6 +1627,11 @@ struct TmpBuf : DevBuf {  // scratch: freed when the call returns, on every path
   ~TmpBuf() { release(); }
 };
 
+inline void swap_buf(DevBuf &a, DevBuf &b) {  // (a TmpBuf on one side frees what the other held)
+  std::swap(a.ptr, b.ptr);
+  std::swap(a.bytes, b.bytes);
+}
+
 // The filtered searches' table L[x] = log(x + 0.5) for x <= n: the entries beyond the current
 // table are computed (glibc, as bm25_idf) and uploaded, the current ones kept.
 int bm25_grow_logtab(cm_bm25 *h, int64_t n) {
@@ -1760,6 +1765,7 @@ int bm25_finish_build(cm_bm25 *h, hipStream_t st) {
 }  // namespace
 
 #include "cm_bm25_append.inc"
+#include "cm_bm25_remove.inc"
 
 extern "C" {
 

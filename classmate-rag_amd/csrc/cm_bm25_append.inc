@@ -128,11 +128,6 @@ __global__ void bm25_append_live_kernel(uint32_t *__restrict__ bits, int64_t n_o
 
 namespace {
 
-inline void swap_buf(DevBuf &a, DevBuf &b) {
-  std::swap(a.ptr, b.ptr);
-  std::swap(a.bytes, b.bytes);
-}
-
 // The shared device path: n_new > 0 documents (device arrays on `st`) after the h->ndocs > 0
 // existing ones.  Nothing of the handle changes before the swap below.
 int bm25_append_device(cm_bm25 *h, const int32_t *term_ids_dev, const int64_t *doc_off_dev, int64_t n_new,

@@ -235,6 +235,23 @@ int cm_bm25_build_dev(cm_bm25 *h, const int32_t *term_ids_dev, const int64_t *do
 int cm_bm25_append(cm_bm25 *h, const int32_t *term_ids, const int64_t *doc_off, int64_t n_new, int32_t vocab);
 int cm_bm25_append_dev(cm_bm25 *h, const int32_t *term_ids_dev, const int64_t *doc_off_dev, int64_t n_new,
                        int64_t ntokens, int32_t vocab, void *stream);
+/* BM25Store.delete_many (rag/retrieval/bm25.py:168-172): remove documents and renumber the
+ * survivors in order (row r becomes r minus the number of removed rows below it), without a
+ * rebuild: a device-side stream compaction of the postings, lengths and live bits.  Afterwards
+ * the handle equals cm_bm25_build over the surviving documents with the same vocab (and, for an
+ * index built with tombstones, the survivors' live flags): exports, statistics and every search,
+ * bit for bit.  rows: n_rows row numbers in [0, ndocs), any order, duplicates allowed (checked on
+ * the host: CM_EINVAL).  Local statistics replace any installed with cm_bm25_set_stats; a
+ * prepared filter table is kept.  n_rows == 0 changes nothing; removing every document leaves
+ * the build of none.  CM_EINVAL and CM_ENOMEM leave the handle as it was; CM_EZERODIV (live
+ * documents remain but no token) is reported with the new state installed, as a build of those
+ * documents reports it.  Peak device memory: old + new postings plus 16 B per 64 postings.
+ * Synchronises, not capturable, no search on the handle meanwhile.  With cm_bm25_timing on, the
+ * two compaction passes' times are the next two cm_bm25_timing_drain entries.                  */
+int cm_bm25_remove(cm_bm25 *h, const int64_t *rows, int64_t n_rows);
+/* The same from a device bitmap: bit r of remove_bits_dev set = remove row r
+ * (ceil(ndocs / 32) words; bits at or above ndocs are ignored; no bit set changes nothing). */
+int cm_bm25_remove_dev(cm_bm25 *h, const uint32_t *remove_bits_dev, void *stream);
 int64_t cm_bm25_num_docs(cm_bm25 *h);
 int64_t cm_bm25_num_postings(cm_bm25 *h);
 /* unfiltered corpus statistics: live docs, total length, avgdl, eps. */
