@@ -1831,7 +1831,7 @@ struct CoarseWs {
   int32_t *fb_mask;   // queries sent to the exact K1 pass (K1q: 2 = the wide re-rank first)
   int32_t *fb_count;
   uint32_t *fb_bound; // K1q: kth_up of a query sent to the wide re-rank
-  int32_t *wide_ctr;  // K1q wide re-rank: [0] slot allocator, [1] queries it finished
+  int32_t *wide_ctr;  // K1q wide re-rank: [0] unused (once the slot allocator), [1] queries it finished
   uint32_t *wide_rows;   // [kWideSlots][kWideCap]
   uint64_t *wide_keys;   // [kWideSlots][kWideCap]
   DenseWs k1;         // the exact K1 pass's own workspace (used only for fb_mask queries)

@@ -1054,7 +1054,10 @@ __global__ void __launch_bounds__(kQRT) dense_rerank_q8_kernel(
     }
     return;
   }
-  if (tid == 0) fb_mask[qi] = 0;
+  if (tid == 0) {
+    fb_mask[qi] = 0;
+    fb_bound[qi] = 0u;   // not sent to the wide re-rank (no kth_up key is 0): its slot ranking counts the others
+  }
   const uint32_t *band_rows = s_rows;   // the rows the fp64 stage re-ranks: the f16 band, or (no full
   int band2 = band;                     // f16 plane, xh_rows_for) the whole int8 band
   if (Xh != nullptr) {
@@ -1217,7 +1220,7 @@ __global__ void __launch_bounds__(kQRT) dense_rerank_q8_kernel(
 // row (the same per-lane arithmetic as dense_rerank_q8_kernel, so the same bits), into a global slot
 // of kWideCap keys; then the k-th smallest distance (radix select), the <= kQSel rows at or below it
 // ranked by full key.  One 1024-thread workgroup per failing query, at most kWideSlots queries per
-// search; beyond that, a band over kWideCap rows or more than kQSel exact ties, the query keeps
+// search (the first by query index); beyond that, a band over kWideCap rows or more than kQSel exact ties, the query keeps
 // fb_mask 1 for the exact pass.  Gated: every workgroup leaves at once when no query failed.
 constexpr int kWideSlots = 16;
 constexpr int kWideCap = 1 << 16;
@@ -1245,12 +1248,21 @@ __global__ void __launch_bounds__(kWideThreads) dense_rerank_wide_kernel(
   __shared__ int s_ovf[kWideOvf];
   __shared__ int s_slot, s_n, s_nsel, s_total, s_novf;
   if (tid == 0) {
-    s_slot = atomicAdd(wide_ctr, 1);
+    s_slot = 0;
     s_n = 0;
     s_nsel = 0;
     s_novf = 0;
   }
   __syncthreads();
+  // slot = this query's rank among the queries the re-rank sent here (fb_bound != 0; written by the
+  // re-rank for every query, only read here): the first kWideSlots of them by query index get a slot,
+  // whatever order the workgroups run in -- an allocator handed them out in arrival order, so with more
+  // than kWideSlots failing queries the same search returned fp64 or fp32-pass distance bits by chance
+  {
+    int before = 0;
+    for (int j = tid; j < qi; j += kWideThreads) before += fb_bound[j] != 0u ? 1 : 0;
+    if (before) atomicAdd(&s_slot, before);
+  }
   if (wave == 0) {  // buffer sizes -> offsets; an overflowed buffer's group is re-scanned below instead
     uint32_t run = 0;
     for (int b0 = 0; b0 < n_wg; b0 += 64) {
@@ -1456,6 +1468,6 @@ __global__ void __launch_bounds__(kWideThreads) dense_rerank_wide_kernel(
   if (tid == 0) {
     fb_mask[qi] = 0;
     atomicSub(fb_count, 1);
-    atomicAdd(wide_ctr + 1, 1);   // [0]: slot allocator, [1]: queries finished here
+    atomicAdd(wide_ctr + 1, 1);   // [1]: queries finished here ([0], once the slot allocator, is unused)
   }
 }
