@@ -96,6 +96,8 @@ SIGNATURES = {
     "cm_bm25_append_dev": (c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp),
     "cm_bm25_remove": (c_int, c_vp, c_vp, c_i64),
     "cm_bm25_remove_dev": (c_int, c_vp, c_vp, c_vp),
+    "cm_bm25_replace": (c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_i32),
+    "cm_bm25_replace_dev": (c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_vp),
     "cm_bm25_num_docs": (c_i64, c_vp),
     "cm_bm25_num_postings": (c_i64, c_vp),
     "cm_bm25_stats": (c_int, c_vp, P(c_i64), P(c_i64), P(c_f64), P(c_f64)),

@@ -367,6 +367,44 @@ class BM25Index:
         L.check(L.fn["cm_bm25_remove_dev"](self._h, L.ptr(bits), _stream(self.device)), "cm_bm25_remove_dev")
         self._ws = None
 
+    def replace(self, rows, term_ids: np.ndarray, doc_off: np.ndarray, vocab: int):
+        """Document i (term_ids[doc_off[i]:doc_off[i + 1]]) takes the place of row rows[i] (distinct
+        rows, any order), without a rebuild (cm_bm25_replace): the index then equals one built over
+        the documents with those rows substituted.  vocab >= the index's."""
+        r = _c(np.asarray(rows).reshape(-1), np.int64)
+        t = _c(term_ids, np.int32)
+        o = _c(doc_off, np.int64)
+        if o.shape[0] != r.shape[0] + 1:
+            raise ValueError("doc_off must have one entry more than rows")
+        try:
+            L.check(L.fn["cm_bm25_replace"](self._h, L.ptr(r), int(r.shape[0]), L.ptr(t), L.ptr(o), int(vocab)),
+                    "cm_bm25_replace")
+        except ZeroDivisionError:  # reported with the new state installed
+            self._replaced(int(r.shape[0]), vocab)
+            raise
+        self._replaced(int(r.shape[0]), vocab)
+
+    def replace_dev(self, rows, term_ids, doc_off, vocab: int):
+        """The same from device tensors on the current stream: rows int64, strictly ascending."""
+        assert rows.dtype == torch.int64 and term_ids.dtype == torch.int32 and doc_off.dtype == torch.int64
+        assert rows.is_contiguous() and term_ids.is_contiguous() and doc_off.is_contiguous()
+        n = int(rows.numel())
+        if int(doc_off.numel()) != n + 1:
+            raise ValueError("doc_off must have one entry more than rows")
+        try:
+            L.check(L.fn["cm_bm25_replace_dev"](self._h, L.ptr(rows), n, L.ptr(term_ids), L.ptr(doc_off),
+                                                int(term_ids.numel()), int(vocab), _stream(self.device)),
+                    "cm_bm25_replace_dev")
+        except ZeroDivisionError:
+            self._replaced(n, vocab)
+            raise
+        self._replaced(n, vocab)
+
+    def _replaced(self, n: int, vocab: int):
+        if n > 0:  # (an empty replace changes nothing, the vocabulary included)
+            self.vocab = int(vocab)
+            self._ws = None  # the cached search workspace's size depends on the range count
+
     @property
     def num_docs(self) -> int:
         return int(L.fn["cm_bm25_num_docs"](self._h))

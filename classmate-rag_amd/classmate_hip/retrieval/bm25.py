@@ -17,7 +17,15 @@ compaction of the postings; no token list, term id or record of a document that
 stays is read).  Between two searches any sequence of deletes and new-id upserts
 is recorded (``_BState.pending_drop`` / ``pending_row``) and applied as at most one
 ``remove`` followed by at most one ``append``.  A replace in place keeps the
-replaced document's row, which neither expresses, and still rebuilds.
+replaced document's row: the ids are recorded too (``_BState.pending_replace``) and
+the next search hands their rows and new term ids to ``engine.BM25Index.replace``
+between the two -- remove, then replace, then append; no other document's tokens
+or term ids are read.  One 4096-chunk file
+replaced in a 10M-chunk index costs 0.17 s against the 25.6 s rebuild, a uniform
+1 % of the chunks 0.20 s (profiles/bm25_replace.txt).  A
+delete that follows a replace before the next search, the first replace on a store
+opened from its sidecar (it parses the catalog, as before) and every replace on the
+sharded index (``multidev.ShardedBM25Index`` has no ``replace``) still rebuild.
 
 Persistence: ``save`` writes the reference's JSONL catalog
 unchanged (bm25.py:220-231) plus a binary sidecar ``<index_file>.cm/`` -- the
@@ -172,6 +180,10 @@ class _BState:
         # search drops them first (engine.BM25Index.remove); pending_row counts in the numbering
         # after that drop.  Together: "drop these device rows, then append the rows from pending_row on"
         self.pending_drop: Optional[np.ndarray] = None
+        # ids replaced in place since the index was current: the next search replaces their rows
+        # (engine.BM25Index.replace) after the drop and before the append; an id whose row lies in
+        # the tail yet to be appended needs nothing, the append reads its current entry
+        self.pending_replace: set = set()
         # tokens of all documents in the store, kept in step by deletes and appends once a delete on
         # the device index has seeded it (None: not known); decides bm25.py:145 without the catalog
         self.ntokens: Optional[int] = None
@@ -340,6 +352,7 @@ class BM25Store:
     _prefix_csr = _proxy("prefix_csr")
     _pending_row = _proxy("pending_row")
     _pending_drop = _proxy("pending_drop")
+    _pending_replace = _proxy("pending_replace")
     _ntokens = _proxy("ntokens")
     _version = _proxy("version")
     _uid = _proxy("uid")
@@ -380,6 +393,7 @@ class BM25Store:
         self._version += 1
         self._csr = self._prefix_csr = None
         self._pending_row = self._pending_drop = self._ntokens = None
+        self._pending_replace = set()
         if self._entries and all(len(e.tokens) == 0 for e in self._entries.values()):
             raise ZeroDivisionError("float division by zero")
         self._dirty = self._meta_dirty = True
@@ -395,22 +409,26 @@ class BM25Store:
             self._prefix_csr, self._csr = self._csr, None
         if all(len(self._entries[i].tokens) == 0 for i in new_ids):   # bm25.py:145 over all entries
             c, tokens = 0, 0
-            if self._prefix_csr is not None:   # the persisted rows' token count stands for their records
+            if self._ntokens is not None:      # the count kept since a delete or replace seeded it
+                c, tokens = n0, self._ntokens
+            elif self._prefix_csr is not None:   # the persisted rows' token count stands for their records
                 c, tokens = len(self._prefix_csr[1]) - 1, int(self._prefix_csr[1][-1])
             if tokens == 0 and all(len(self._entries[i].tokens) == 0 for i in self._id_list[c:n0]):
                 raise ZeroDivisionError("float division by zero")
         if self._ntokens is not None:
             self._ntokens += sum(len(self._entries[i].tokens) for i in new_ids)
-        # the index is current, or lacks only rows to drop: from now on it also lacks the rows from n0 on
+        # the index is current, or lacks only rows to drop or replace: from now on it also lacks the
+        # rows from n0 on
         if (self._index is not None and self._pending_row is None
-                and (not self._dirty or self._pending_drop is not None)):
+                and (not self._dirty or self._pending_drop is not None or self._pending_replace)):
             self._pending_row = n0
         self._dirty = True
 
     def _removable(self) -> bool:
         """delete_many may leave the device index in place: there is one, it is current or lacks only
-        what this mechanism has pending (rows to drop, rows to append), and it can drop rows."""
-        return (self._index is not None and hasattr(self._index, "remove")
+        what this mechanism has pending (rows to drop, rows to append), and it can drop rows.  Pending
+        replaces are applied to rows in the numbering before the delete: a delete after them rebuilds."""
+        return (self._index is not None and hasattr(self._index, "remove") and not self._pending_replace
                 and (not self._dirty or self._pending_row is not None or self._pending_drop is not None))
 
     def _removed(self, popped: Sequence[tuple]) -> None:
@@ -446,9 +464,27 @@ class BM25Store:
         if self._ntokens == 0:                 # bm25.py:145: documents remain, every token list is empty
             raise ZeroDivisionError("float division by zero")
 
-    def _rows_csr(self, r0: int):
-        """(term ids, offsets from 0) of rows [r0, n) from their entries."""
-        entries = [self._entries[i] for i in self._id_list[r0:]]
+    def _replaceable(self) -> bool:
+        """upsert_many may leave the device index in place when it replaces documents: there is one,
+        it is current or lacks only what this mechanism has pending (rows to drop, rows to append,
+        earlier replaces), and it can replace rows.  A catalog opened from a sidecar and not parsed
+        yet keeps the rebuild, which parses it (tests/test_gpu_dropin.py holds a replace to that)."""
+        return (self._index is not None and hasattr(self._index, "replace")
+                and not getattr(self._entries, "pending", False)
+                and (not self._dirty or self._pending_row is not None or self._pending_drop is not None
+                     or bool(self._pending_replace)))
+
+    def _seed_ntokens(self) -> None:
+        """The token count of all documents, from the index's own count plus the tail it does not hold
+        yet (before any entry is overwritten; nothing is pending but that tail while it is None)."""
+        if self._ntokens is None:
+            have = len(self._id_list) if self._pending_row is None else self._pending_row
+            self._ntokens = int(self._index.stats()["sum_len"]) + sum(
+                len(self._entries[i].tokens) for i in self._id_list[have:])
+
+    def _rows_csr(self, r0: int, ids: Optional[Sequence[str]] = None):
+        """(term ids, offsets from 0) of rows [r0, n) -- or of the documents ``ids`` -- from their entries."""
+        entries = [self._entries[i] for i in (self._id_list[r0:] if ids is None else ids)]
         for e in entries:
             if e.term_ids is None:
                 e.term_ids = self._term_ids(e.tokens)
@@ -466,6 +502,7 @@ class BM25Store:
         n = len(self._id_list)
         drop = self._pending_drop  # device rows to drop first, when deletes are pending
         have = self._pending_row   # rows the device index holds (after that drop), when it is a prefix of the store
+        repl = self._pending_replace  # ids whose rows the device index holds with an earlier text
         if drop is not None:
             if have is None:
                 have = n
@@ -473,6 +510,15 @@ class BM25Store:
                 self._index.remove(drop)
             else:
                 have = None
+        elif have is None and repl:
+            have = n
+        if repl and have is not None and self._index.num_docs == have and hasattr(self._index, "replace"):
+            # after the drop the device rows [0, have) are id_list[:have]; a rebuild below reads the
+            # current entries and needs none of this
+            rows = [r for r, i in enumerate(self._id_list[:have]) if i in repl]
+            if rows:
+                flat, off = self._rows_csr(0, [self._id_list[r] for r in rows])   # (assigns new terms' ids)
+                self._index.replace(np.asarray(rows, np.int64), flat, off, max(len(self._vocab), 1))
         if have is None or self._index.num_docs != have:
             csr = self._csr if self._csr is not None else self._prefix_csr
             if csr is not None:  # opened from a sidecar: the persisted CSR is the index (of its rows)
@@ -489,6 +535,7 @@ class BM25Store:
             flat, off = self._rows_csr(have)
             self._index.append(flat, off, max(len(self._vocab), 1))
         self._pending_row = self._pending_drop = None
+        self._pending_replace = set()
         self._dirty = False
 
     def _ensure_meta(self) -> None:
@@ -507,22 +554,18 @@ class BM25Store:
             raise ValueError("ids, texts, metadatas must have the same length")
         self._mutating()
         st = self._st
+        if self._replaceable() and any(i in self._entries for i in ids):
+            return self._upsert_replacing(ids, texts, metadatas)
         n0 = len(self._entries)
         appended = []                  # (row, metadata) of documents new to the store, in insertion order
         for i, doc_id in enumerate(ids):
-            text = texts[i] or ""
-            meta = dict(metadatas[i] or {})
-            lang = meta.get("language")
-            if not lang or lang == "auto":
-                lang = detect_lang_tag(text)
-                meta["language"] = lang
-            toks = _tokenize(text, lang_hint=lang)
+            meta, toks = self._tokenized(texts[i], metadatas[i])
             if doc_id in self._entries:  # replaced in place: the saved records are no longer a prefix
                 st.append_only = False
                 appended = None
             elif appended is not None:
                 appended.append((n0 + len(appended), meta))
-            self._entries[doc_id] = _Entry(id=doc_id, text=text, tokens=toks, metadata=meta)
+            self._entries[doc_id] = _Entry(id=doc_id, text=texts[i] or "", tokens=toks, metadata=meta)
         meta_ok = not self._meta_dirty
         if appended is not None:
             self._appended(list(ids))
@@ -532,6 +575,54 @@ class BM25Store:
             for r, meta in appended:
                 self._meta.set(r, meta)
             self._meta_dirty = False
+
+    @staticmethod
+    def _tokenized(text, metadata):
+        """bm25.py:152-160: (metadata with the language filled in, tokens) of one document."""
+        text = text or ""
+        meta = dict(metadata or {})
+        lang = meta.get("language")
+        if not lang or lang == "auto":
+            lang = detect_lang_tag(text)
+            meta["language"] = lang
+        return meta, _tokenize(text, lang_hint=lang)
+
+    def _upsert_replacing(self, ids, texts, metadatas) -> None:
+        """upsert_many with ids the store holds, on an index that _replaceable(): the replaced ids
+        are recorded for _ensure_index, the ids new to the store go through _appended, each once
+        and in first-appearance order.  No other document's tokens or term ids are read."""
+        st = self._st
+        st.append_only = False         # the saved records are no longer a prefix
+        meta_ok = not self._meta_dirty
+        held = {i for i in ids if i in self._entries}
+        row_of = {i: r for r, i in enumerate(self._id_list) if i in held} if meta_ok else {}
+        n0 = len(self._id_list)
+        self._seed_ntokens()
+        new_ids, new_meta = [], {}
+        for i, doc_id in enumerate(ids):
+            meta, toks = self._tokenized(texts[i], metadatas[i])
+            if doc_id in new_meta:     # given twice: its row is yet to be appended, with its last text
+                new_meta[doc_id] = meta
+            elif doc_id in self._entries:
+                old = self._entries[doc_id]
+                self._ntokens += len(toks) - len(old.tokens)
+                if meta_ok:            # MetaIndex.set clears the row's old values: while the old entry stands
+                    self._meta.set(row_of[doc_id], meta)
+                self._pending_replace.add(doc_id)
+            else:
+                new_ids.append(doc_id)
+                new_meta[doc_id] = meta
+            self._entries[doc_id] = _Entry(id=doc_id, text=texts[i] or "", tokens=toks, metadata=meta)
+        self._version += 1
+        self._csr = self._prefix_csr = None            # the persisted CSR no longer describes those rows
+        self._dirty = True
+        if new_ids:
+            self._appended(new_ids)
+            if meta_ok:
+                for r, doc_id in enumerate(new_ids, n0):
+                    self._meta.set(r, new_meta[doc_id])
+        if self._ntokens == 0:                         # bm25.py:145: every token list is empty
+            raise ZeroDivisionError("float division by zero")
 
     @_locked
     def delete_many(self, ids: Sequence[str]) -> None:

@@ -1766,6 +1766,7 @@ int bm25_finish_build(cm_bm25 *h, hipStream_t st) {
 
 #include "cm_bm25_append.inc"
 #include "cm_bm25_remove.inc"
+#include "cm_bm25_replace.inc"
 
 extern "C" {
 

@@ -252,6 +252,31 @@ int cm_bm25_remove(cm_bm25 *h, const int64_t *rows, int64_t n_rows);
 /* The same from a device bitmap: bit r of remove_bits_dev set = remove row r
  * (ceil(ndocs / 32) words; bits at or above ndocs are ignored; no bit set changes nothing). */
 int cm_bm25_remove_dev(cm_bm25 *h, const uint32_t *remove_bits_dev, void *stream);
+/* BM25Store.upsert_many for ids the store already holds (rag/retrieval/bm25.py:147-166: the dict
+ * assignment keeps the document's row): document i, the tokens term_ids[doc_off[i] .. doc_off[i+1])
+ * (doc_off[0] == 0, term ids in [0, vocab), vocab >= the index's: new terms may arrive with the
+ * replacement), takes the place of row rows[i], without a rebuild: the replaced rows' postings are
+ * dropped and the new texts' postings, built on the device, are scattered between each term's
+ * surviving ones.  Afterwards the handle equals cm_bm25_build over the same documents with those
+ * rows substituted and the same vocab; the replaced rows are live, every other row keeps its live
+ * flag (tombstones of a build with `live` included): exports, cm_bm25_stats, cm_bm25_term_stats,
+ * the head-term count and every search, bit for bit.  rows: n_rows distinct row numbers in
+ * [0, ndocs), any order (a duplicate or out-of-range row: CM_EINVAL, checked on the host; the host
+ * sorts the documents by row before upload).  Local statistics replace any installed with
+ * cm_bm25_set_stats; a prepared filter table is kept; ndocs does not change.  n_rows == 0 changes
+ * nothing.  CM_EINVAL, CM_ENOMEM and CM_EUNSUPPORTED (a tf above 65535) leave the handle as it
+ * was; CM_EZERODIV (live documents but no token) is reported with the new state installed, as
+ * cm_bm25_remove does.  Peak device memory: old + new postings, 16 B per 64 postings, the delta
+ * and its sort scratch.  Synchronises, not capturable, no search on the handle meanwhile.  With
+ * cm_bm25_timing on, the flag pass with its scan and the scatter passes are the next two
+ * cm_bm25_timing_drain entries.                                                               */
+int cm_bm25_replace(cm_bm25 *h, const int64_t *rows, int64_t n_rows, const int32_t *term_ids, const int64_t *doc_off,
+                    int32_t vocab);
+/* The same from device arrays (ntokens = doc_off_dev[n_rows]).  rows_dev must be strictly
+ * ascending and within [0, ndocs): checked on the device, with a flag read back before anything
+ * is modified (CM_EINVAL). */
+int cm_bm25_replace_dev(cm_bm25 *h, const int64_t *rows_dev, int64_t n_rows, const int32_t *term_ids_dev,
+                        const int64_t *doc_off_dev, int64_t ntokens, int32_t vocab, void *stream);
 int64_t cm_bm25_num_docs(cm_bm25 *h);
 int64_t cm_bm25_num_postings(cm_bm25 *h);
 /* unfiltered corpus statistics: live docs, total length, avgdl, eps. */
