@@ -337,18 +337,21 @@ class BM25Index:
         o = _c(doc_off, np.int64)
         n_new = int(o.shape[0] - 1)
         L.check(L.fn["cm_bm25_append"](self._h, L.ptr(t), L.ptr(o), n_new, int(vocab)), "cm_bm25_append")
-        self._appended(n_new, vocab)
+        self._mutated(n_new, vocab)
 
     def append_dev(self, term_ids, doc_off, vocab: int):
         assert term_ids.dtype == torch.int32 and doc_off.dtype == torch.int64
         n_new = int(doc_off.numel() - 1)
         L.check(L.fn["cm_bm25_append_dev"](self._h, L.ptr(term_ids), L.ptr(doc_off), n_new, int(term_ids.numel()),
                                            int(vocab), _stream(self.device)), "cm_bm25_append_dev")
-        self._appended(n_new, vocab)
+        self._mutated(n_new, vocab)
 
-    def _appended(self, n_new: int, vocab: int):
-        if n_new > 0:  # (an empty append changes nothing, the vocabulary included)
-            self.vocab = int(vocab)
+    def _mutated(self, n: int, vocab: Optional[int] = None):
+        """After an append, remove or replace of n documents (an empty one changes nothing, the
+        vocabulary included)."""
+        if n > 0:
+            if vocab is not None:
+                self.vocab = int(vocab)
             self._ws = None  # the cached search workspace's size depends on the range count
 
     def remove(self, rows):
@@ -357,7 +360,7 @@ class BM25Index:
         over the surviving documents."""
         r = _c(np.asarray(rows).reshape(-1), np.int64)
         L.check(L.fn["cm_bm25_remove"](self._h, L.ptr(r), int(r.shape[0])), "cm_bm25_remove")
-        self._ws = None  # the cached search workspace's size depends on the range count
+        self._mutated(int(r.shape[0]))
 
     def remove_dev(self, bits):
         """The same from a device bitmap: int32/uint32 tensor of ceil(num_docs / 32) words, bit r of
@@ -365,7 +368,7 @@ class BM25Index:
         assert bits.is_cuda and bits.element_size() == 4 and not bits.dtype.is_floating_point and bits.is_contiguous()
         assert bits.numel() == (self.num_docs + 31) // 32
         L.check(L.fn["cm_bm25_remove_dev"](self._h, L.ptr(bits), _stream(self.device)), "cm_bm25_remove_dev")
-        self._ws = None
+        self._ws = None  # (how many bits were set is not known here)
 
     def replace(self, rows, term_ids: np.ndarray, doc_off: np.ndarray, vocab: int):
         """Document i (term_ids[doc_off[i]:doc_off[i + 1]]) takes the place of row rows[i] (distinct
@@ -379,10 +382,11 @@ class BM25Index:
         try:
             L.check(L.fn["cm_bm25_replace"](self._h, L.ptr(r), int(r.shape[0]), L.ptr(t), L.ptr(o), int(vocab)),
                     "cm_bm25_replace")
-        except ZeroDivisionError:  # reported with the new state installed
-            self._replaced(int(r.shape[0]), vocab)
+        # the new state is installed when this is reported; build and append do not record it (to be fixed on its own)
+        except ZeroDivisionError:
+            self._mutated(int(r.shape[0]), vocab)
             raise
-        self._replaced(int(r.shape[0]), vocab)
+        self._mutated(int(r.shape[0]), vocab)
 
     def replace_dev(self, rows, term_ids, doc_off, vocab: int):
         """The same from device tensors on the current stream: rows int64, strictly ascending."""
@@ -396,14 +400,9 @@ class BM25Index:
                                                 int(term_ids.numel()), int(vocab), _stream(self.device)),
                     "cm_bm25_replace_dev")
         except ZeroDivisionError:
-            self._replaced(n, vocab)
+            self._mutated(n, vocab)
             raise
-        self._replaced(n, vocab)
-
-    def _replaced(self, n: int, vocab: int):
-        if n > 0:  # (an empty replace changes nothing, the vocabulary included)
-            self.vocab = int(vocab)
-            self._ws = None  # the cached search workspace's size depends on the range count
+        self._mutated(n, vocab)
 
     @property
     def num_docs(self) -> int:

@@ -9,23 +9,24 @@ duplicate query tokens counted twice (Q3), zero-score padding in insertion
 order (Q1), ZeroDivisionError on an all-empty vocabulary (Q7).
 
 The reference rebuilds BM25Okapi on every mutation and again per search; here
-mutations mark the device index dirty and the next search rebuilds it once --
-or, after upserts of ids new to the store only, appends their rows to it
-(``engine.BM25Index.append``: no pass over the documents already indexed), and
-after deletes drops their rows from it (``engine.BM25Index.remove``: a device-side
-compaction of the postings; no token list, term id or record of a document that
-stays is read).  Between two searches any sequence of deletes and new-id upserts
-is recorded (``_BState.pending_drop`` / ``pending_row``) and applied as at most one
-``remove`` followed by at most one ``append``.  A replace in place keeps the
-replaced document's row: the ids are recorded too (``_BState.pending_replace``) and
-the next search hands their rows and new term ids to ``engine.BM25Index.replace``
-between the two -- remove, then replace, then append; no other document's tokens
-or term ids are read.  One 4096-chunk file
-replaced in a 10M-chunk index costs 0.17 s against the 25.6 s rebuild, a uniform
-1 % of the chunks 0.20 s (profiles/bm25_replace.txt).  A
-delete that follows a replace before the next search, the first replace on a store
-opened from its sidecar (it parses the catalog, as before) and every replace on the
-sharded index (``multidev.ShardedBM25Index`` has no ``replace``) still rebuild.
+mutations mark the device index dirty and the next search brings it up to date
+once.  What happened since the last search decides how:
+
+* left in place (no token list, term id or record of a document that stays is read):
+  - upserts of ids new to the store: their rows are appended (``engine.BM25Index.append``);
+  - deletes: their rows are dropped (``engine.BM25Index.remove``, a device-side compaction
+    of the postings);
+  - upserts of ids the store holds: the documents keep their rows
+    (``engine.BM25Index.replace``).  One 4096-chunk file replaced in a 10M-chunk index
+    costs 0.17 s against the 25.6 s rebuild, a uniform 1 % of the chunks 0.20 s
+    (profiles/bm25_replace.txt).
+* still a rebuild:
+  - a delete that follows a replace before the next search;
+  - the first replace on a store opened from its sidecar (it parses the catalog, as before);
+  - every replace on the sharded index (``multidev.ShardedBM25Index`` has no ``replace``).
+* order: any sequence of such calls between two searches is recorded
+  (``_BState.pending_drop`` / ``pending_replace`` / ``pending_row``) and applied as at
+  most one ``remove``, then at most one ``replace``, then at most one ``append``.
 
 Persistence: ``save`` writes the reference's JSONL catalog
 unchanged (bm25.py:220-231) plus a binary sidecar ``<index_file>.cm/`` -- the
@@ -391,12 +392,21 @@ class BM25Store:
         entries exist but every token list is empty.  We check that and defer the device build."""
         self._id_list = list(self._entries.keys())
         self._version += 1
-        self._csr = self._prefix_csr = None
-        self._pending_row = self._pending_drop = self._ntokens = None
-        self._pending_replace = set()
+        self._csr = self._prefix_csr = self._ntokens = None
+        self._clear_pending()
         if self._entries and all(len(e.tokens) == 0 for e in self._entries.values()):
             raise ZeroDivisionError("float division by zero")
         self._dirty = self._meta_dirty = True
+
+    def _clear_pending(self) -> None:
+        self._pending_row = self._pending_drop = None
+        self._pending_replace = set()
+
+    def _tracked(self) -> bool:
+        """The device index exists and is current, or lacks only what is recorded as pending (rows to
+        drop, rows to replace, rows to append)."""
+        return self._index is not None and (not self._dirty or self._pending_row is not None
+                                            or self._pending_drop is not None or bool(self._pending_replace))
 
     def _appended(self, new_ids: Sequence[str]) -> None:
         """_rebuild after an upsert of ids new to the store only: they are the rows after the existing
@@ -417,19 +427,14 @@ class BM25Store:
                 raise ZeroDivisionError("float division by zero")
         if self._ntokens is not None:
             self._ntokens += sum(len(self._entries[i].tokens) for i in new_ids)
-        # the index is current, or lacks only rows to drop or replace: from now on it also lacks the
-        # rows from n0 on
-        if (self._index is not None and self._pending_row is None
-                and (not self._dirty or self._pending_drop is not None or self._pending_replace)):
+        if self._tracked() and self._pending_row is None:   # from now on the index also lacks the rows from n0 on
             self._pending_row = n0
         self._dirty = True
 
     def _removable(self) -> bool:
-        """delete_many may leave the device index in place: there is one, it is current or lacks only
-        what this mechanism has pending (rows to drop, rows to append), and it can drop rows.  Pending
+        """delete_many may leave the device index in place: it is _tracked() and can drop rows.  Pending
         replaces are applied to rows in the numbering before the delete: a delete after them rebuilds."""
-        return (self._index is not None and hasattr(self._index, "remove") and not self._pending_replace
-                and (not self._dirty or self._pending_row is not None or self._pending_drop is not None))
+        return self._tracked() and not self._pending_replace and hasattr(self._index, "remove")
 
     def _removed(self, popped: Sequence[tuple]) -> None:
         """_rebuild after a delete, on an index that _removable(): the popped documents' rows are
@@ -439,10 +444,7 @@ class BM25Store:
         gone = dict(popped)
         old_ids = self._id_list
         n0 = len(old_ids)
-        if self._ntokens is None:   # seed: the index's own count, plus the tail it does not hold yet
-            have = n0 if self._pending_row is None else self._pending_row
-            self._ntokens = int(self._index.stats()["sum_len"]) + sum(
-                len((gone.get(i) or self._entries[i]).tokens) for i in old_ids[have:])
+        self._seed_ntokens(gone)
         self._ntokens -= sum(len(e.tokens) for e in gone.values())
         rows = np.fromiter((r for r, i in enumerate(old_ids) if i in gone), np.int64)
         self._id_list = [i for i in old_ids if i not in gone]
@@ -465,22 +467,20 @@ class BM25Store:
             raise ZeroDivisionError("float division by zero")
 
     def _replaceable(self) -> bool:
-        """upsert_many may leave the device index in place when it replaces documents: there is one,
-        it is current or lacks only what this mechanism has pending (rows to drop, rows to append,
-        earlier replaces), and it can replace rows.  A catalog opened from a sidecar and not parsed
-        yet keeps the rebuild, which parses it (tests/test_gpu_dropin.py holds a replace to that)."""
-        return (self._index is not None and hasattr(self._index, "replace")
-                and not getattr(self._entries, "pending", False)
-                and (not self._dirty or self._pending_row is not None or self._pending_drop is not None
-                     or bool(self._pending_replace)))
+        """upsert_many may leave the device index in place when it replaces documents: it is
+        _tracked() and can replace rows.  A catalog opened from a sidecar and not parsed yet keeps
+        the rebuild, which parses it (tests/test_gpu_dropin.py holds a replace to that)."""
+        return (self._tracked() and hasattr(self._index, "replace")
+                and not getattr(self._entries, "pending", False))
 
-    def _seed_ntokens(self) -> None:
+    def _seed_ntokens(self, gone: Optional[Mapping[str, _Entry]] = None) -> None:
         """The token count of all documents, from the index's own count plus the tail it does not hold
-        yet (before any entry is overwritten; nothing is pending but that tail while it is None)."""
+        yet (before any entry is overwritten and while the id list still names the documents in
+        ``gone``, popped from the catalog; nothing is pending but that tail while it is None)."""
         if self._ntokens is None:
             have = len(self._id_list) if self._pending_row is None else self._pending_row
             self._ntokens = int(self._index.stats()["sum_len"]) + sum(
-                len(self._entries[i].tokens) for i in self._id_list[have:])
+                len(((gone and gone.get(i)) or self._entries[i]).tokens) for i in self._id_list[have:])
 
     def _rows_csr(self, r0: int, ids: Optional[Sequence[str]] = None):
         """(term ids, offsets from 0) of rows [r0, n) -- or of the documents ``ids`` -- from their entries."""
@@ -534,8 +534,7 @@ class BM25Store:
         if have < n:
             flat, off = self._rows_csr(have)
             self._index.append(flat, off, max(len(self._vocab), 1))
-        self._pending_row = self._pending_drop = None
-        self._pending_replace = set()
+        self._clear_pending()
         self._dirty = False
 
     def _ensure_meta(self) -> None:
@@ -549,32 +548,57 @@ class BM25Store:
 
     @_locked
     def upsert_many(self, *, ids: Sequence[str], texts: Sequence[str], metadatas: Sequence[Mapping[str, Any]]) -> None:
-        """bm25.py:147-166: language from metadata (or detected), tokenize, replace in place."""
+        """bm25.py:147-166: language from metadata (or detected), tokenize, replace in place.
+
+        Each id is new to the store (its row is appended: once, with the last text given for it),
+        or the store holds it (it keeps its row).  On an index that _replaceable() the replaced ids
+        are recorded for _ensure_index and no other document's tokens or term ids are read; on any
+        other, an id the store holds or one given twice rebuilds."""
         if not (len(ids) == len(texts) == len(metadatas)):
             raise ValueError("ids, texts, metadatas must have the same length")
         self._mutating()
         st = self._st
-        if self._replaceable() and any(i in self._entries for i in ids):
-            return self._upsert_replacing(ids, texts, metadatas)
-        n0 = len(self._entries)
-        appended = []                  # (row, metadata) of documents new to the store, in insertion order
+        in_place = self._replaceable() and any(i in self._entries for i in ids)
+        meta_ok = not self._meta_dirty
+        n0 = len(self._id_list)
+        if in_place:
+            held = {i for i in ids if i in self._entries}
+            row_of = {i: r for r, i in enumerate(self._id_list) if i in held} if meta_ok else {}
+            self._seed_ntokens()
+        new_ids, new_meta, only_new = [], {}, True
         for i, doc_id in enumerate(ids):
             meta, toks = self._tokenized(texts[i], metadatas[i])
-            if doc_id in self._entries:  # replaced in place: the saved records are no longer a prefix
-                st.append_only = False
-                appended = None
-            elif appended is not None:
-                appended.append((n0 + len(appended), meta))
+            if doc_id not in self._entries:
+                new_ids.append(doc_id)
+                new_meta[doc_id] = meta
+            else:
+                only_new = st.append_only = False   # the saved records are no longer a prefix
+                if doc_id in new_meta:     # given twice: its row is yet to be appended, with its last text
+                    new_meta[doc_id] = meta
+                elif in_place:
+                    self._ntokens += len(toks) - len(self._entries[doc_id].tokens)
+                    if meta_ok:            # MetaIndex.set clears the row's old values: while the old entry stands
+                        self._meta.set(row_of[doc_id], meta)
+                    self._pending_replace.add(doc_id)
             self._entries[doc_id] = _Entry(id=doc_id, text=texts[i] or "", tokens=toks, metadata=meta)
-        meta_ok = not self._meta_dirty
-        if appended is not None:
-            self._appended(list(ids))
-        else:
-            self._rebuild()
-        if meta_ok and appended is not None:   # the filter columns follow the appended rows
-            for r, meta in appended:
-                self._meta.set(r, meta)
-            self._meta_dirty = False
+        # What is left to do, by case:
+        #   in place (with or without new ids): mark the index stale here, append the new ids below,
+        #     and check bm25.py:145 last, against the token count kept since _seed_ntokens;
+        #   not in place, an id held or given twice: the rebuild, which does all of it;
+        #   not in place, new ids only (or no id at all): _appended alone, which marks and checks.
+        if in_place:
+            self._version += 1
+            self._csr = self._prefix_csr = None        # the persisted CSR no longer describes those rows
+            self._dirty = True
+        elif not only_new:
+            return self._rebuild()
+        if new_ids or not in_place:
+            self._appended(new_ids)
+            if meta_ok:                                # the filter columns follow the appended rows
+                for r, doc_id in enumerate(new_ids, n0):
+                    self._meta.set(r, new_meta[doc_id])
+        if in_place and self._ntokens == 0:            # bm25.py:145: every token list is empty
+            raise ZeroDivisionError("float division by zero")
 
     @staticmethod
     def _tokenized(text, metadata):
@@ -586,43 +610,6 @@ class BM25Store:
             lang = detect_lang_tag(text)
             meta["language"] = lang
         return meta, _tokenize(text, lang_hint=lang)
-
-    def _upsert_replacing(self, ids, texts, metadatas) -> None:
-        """upsert_many with ids the store holds, on an index that _replaceable(): the replaced ids
-        are recorded for _ensure_index, the ids new to the store go through _appended, each once
-        and in first-appearance order.  No other document's tokens or term ids are read."""
-        st = self._st
-        st.append_only = False         # the saved records are no longer a prefix
-        meta_ok = not self._meta_dirty
-        held = {i for i in ids if i in self._entries}
-        row_of = {i: r for r, i in enumerate(self._id_list) if i in held} if meta_ok else {}
-        n0 = len(self._id_list)
-        self._seed_ntokens()
-        new_ids, new_meta = [], {}
-        for i, doc_id in enumerate(ids):
-            meta, toks = self._tokenized(texts[i], metadatas[i])
-            if doc_id in new_meta:     # given twice: its row is yet to be appended, with its last text
-                new_meta[doc_id] = meta
-            elif doc_id in self._entries:
-                old = self._entries[doc_id]
-                self._ntokens += len(toks) - len(old.tokens)
-                if meta_ok:            # MetaIndex.set clears the row's old values: while the old entry stands
-                    self._meta.set(row_of[doc_id], meta)
-                self._pending_replace.add(doc_id)
-            else:
-                new_ids.append(doc_id)
-                new_meta[doc_id] = meta
-            self._entries[doc_id] = _Entry(id=doc_id, text=texts[i] or "", tokens=toks, metadata=meta)
-        self._version += 1
-        self._csr = self._prefix_csr = None            # the persisted CSR no longer describes those rows
-        self._dirty = True
-        if new_ids:
-            self._appended(new_ids)
-            if meta_ok:
-                for r, doc_id in enumerate(new_ids, n0):
-                    self._meta.set(r, new_meta[doc_id])
-        if self._ntokens == 0:                         # bm25.py:145: every token list is empty
-            raise ZeroDivisionError("float division by zero")
 
     @_locked
     def delete_many(self, ids: Sequence[str]) -> None:

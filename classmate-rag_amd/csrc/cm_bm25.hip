@@ -1632,6 +1632,19 @@ inline void swap_buf(DevBuf &a, DevBuf &b) {  // (a TmpBuf on one side frees wha
   std::swap(a.bytes, b.bytes);
 }
 
+// out[i] = in[0] + ... + in[i - 1] (hipcub), in place when out == in.  `tmp` is the library's
+// scratch: DevBuf::ensure grows a buffer that is too small, so one TmpBuf serves a call's every
+// library step, whatever their order.
+template <typename In, typename Out>
+int bm25_exclusive_sum(TmpBuf &tmp, In in, Out out, int64_t n, hipStream_t st) {
+  size_t need = 0;
+  CM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, in, out, n, st));
+  const int rc = tmp.ensure(need);
+  if (rc) return rc;
+  CM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.ptr, need, in, out, n, st));
+  return CM_OK;
+}
+
 // The filtered searches' table L[x] = log(x + 0.5) for x <= n: the entries beyond the current
 // table are computed (glibc, as bm25_idf) and uploaded, the current ones kept.
 int bm25_grow_logtab(cm_bm25 *h, int64_t n) {
@@ -1687,10 +1700,7 @@ int bm25_csr_from_tokens(hipStream_t st, const int32_t *term_ids_dev, const int6
   int32_t *cnt = reinterpret_cast<int32_t *>(vbuf.Alternate());
   size_t tmp2 = 0;
   CM_HIP(hipcub::DeviceRunLengthEncode::Encode(nullptr, tmp2, sk, uk, cnt, nruns_d.as<int64_t>(), ntokens, st));
-  if (tmp2 > cub_tmp.bytes) {
-    cub_tmp.release();
-    if ((rc = cub_tmp.ensure(tmp2))) return rc;
-  }
+  if ((rc = cub_tmp.ensure(tmp2))) return rc;
   CM_HIP(hipcub::DeviceRunLengthEncode::Encode(cub_tmp.ptr, tmp2, sk, uk, cnt, nruns_d.as<int64_t>(), ntokens, st));
   int64_t nruns = 0;
   int32_t hflags[2] = {0, 0};
@@ -1701,16 +1711,8 @@ int bm25_csr_from_tokens(hipStream_t st, const int32_t *term_ids_dev, const int6
   if (hflags[0] & 2) CM_FAIL(CM_EINVAL, "doc_off must be non-decreasing within [0, ntokens]");
   if ((rc = runstart.ensure((size_t)std::max<int64_t>(nruns, 1) * 8))) return rc;
   // run_start = exclusive scan of counts (as int64)
-  {
-    size_t tmp3 = 0;
-    auto in = hipcub::TransformInputIterator<int64_t, hipcub::CastOp<int64_t>, int32_t *>(cnt, hipcub::CastOp<int64_t>());
-    CM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp3, in, runstart.as<int64_t>(), nruns, st));
-    if (tmp3 > cub_tmp.bytes) {
-      cub_tmp.release();
-      if ((rc = cub_tmp.ensure(tmp3))) return rc;
-    }
-    CM_HIP(hipcub::DeviceScan::ExclusiveSum(cub_tmp.ptr, tmp3, in, runstart.as<int64_t>(), nruns, st));
-  }
+  auto cnt64 = hipcub::TransformInputIterator<int64_t, hipcub::CastOp<int64_t>, int32_t *>(cnt, hipcub::CastOp<int64_t>());
+  if ((rc = bm25_exclusive_sum(cub_tmp, cnt64, runstart.as<int64_t>(), nruns, st))) return rc;
   if ((rc = post_doc.ensure((size_t)std::max<int64_t>(nruns, 1) * 4)) ||
       (rc = post_tf.ensure((size_t)std::max<int64_t>(nruns, 1) * 2)) ||
       (rc = post_pos.ensure((size_t)std::max<int64_t>(nruns, 1) * 4)) ||
@@ -1764,6 +1766,7 @@ int bm25_finish_build(cm_bm25 *h, hipStream_t st) {
 
 }  // namespace
 
+#include "cm_bm25_mutate.inc"
 #include "cm_bm25_append.inc"
 #include "cm_bm25_remove.inc"
 #include "cm_bm25_replace.inc"
@@ -1814,12 +1817,9 @@ int cm_bm25_build(cm_bm25 *h, const int32_t *term_ids, const int64_t *doc_off, i
   if (ndocs < 0 || vocab < 0 || (ndocs > 0 && !doc_off)) CM_FAIL(CM_EINVAL, "bad arguments");
   if (ndocs >= (int64_t)INT32_MAX) CM_FAIL(CM_EINVAL, "too many docs for one shard");
   DeviceGuard dg(h->dev);
-  const int64_t ntok = ndocs ? doc_off[ndocs] : 0;
-  if (ntok > 0 && !term_ids) CM_FAIL(CM_EINVAL, "term_ids is NULL");
-  for (int64_t d = 0; d < ndocs; ++d)
-    if (doc_off[d + 1] < doc_off[d]) CM_FAIL(CM_EINVAL, "doc_off must be non-decreasing");
-  for (int64_t p = 0; p < ntok; ++p)
-    if (term_ids[p] < 0 || term_ids[p] >= vocab) CM_FAIL(CM_EINVAL, "term id out of range");
+  if (ndocs && doc_off[ndocs] > 0 && !term_ids) CM_FAIL(CM_EINVAL, "term_ids is NULL");  // (here: before the offsets)
+  const int64_t ntok = bm25_checked_ntok(term_ids, doc_off, ndocs, vocab);
+  if (ntok < 0) return CM_EINVAL;
   // pass 1: df over live docs, first-occurrence order, lengths
   std::vector<int64_t> stamp((size_t)vocab, -1);
   std::vector<int32_t> df((size_t)vocab, 0), order;

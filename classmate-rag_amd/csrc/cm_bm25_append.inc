@@ -2,11 +2,9 @@
 //
 // The new documents take the rows after the existing ones, so every term's new postings follow
 // its old ones.  K7's first half (bm25_csr_from_tokens) turns the new tokens into a delta CSR in
-// scratch; one kernel adds the offsets (term_off'[t] = term_off[min(t, V_old)] + delta_off[t]) and
-// one streams both posting sets into fresh arrays, each term's old run followed by its delta run.
-// The fresh arrays replace the old ones only after everything that can fail on the way has not;
-// K7's second half (bm25_finish_build) then recomputes df, the idf table and the head tiles as a
-// build does, which is what makes the handle bit-equal to one built over all documents.
+// scratch; the offsets add up (term_off'[t] = term_off[min(t, V_old)] + delta_off[t]) and one kernel
+// streams both posting sets into fresh arrays, each term's old run followed by its delta run.  The
+// steps around that are the plan all three mutations share: cm_bm25_mutate.inc.
 //
 // Peak device memory: old + new postings (10 B each) plus the delta's sort scratch; the old arrays
 // are freed when the call returns.
@@ -16,26 +14,6 @@ namespace cm {
 constexpr int kAppThreads = 256;
 constexpr int kAppGroups = 4;  // groups of 4 consecutive postings per thread
 constexpr int64_t kAppChunk = (int64_t)kAppThreads * 4 * kAppGroups;  // output postings per workgroup
-
-__global__ void bm25_append_offsets_kernel(const int64_t *__restrict__ old_off, int32_t v_old,
-                                           const int64_t *__restrict__ delta_off, int32_t v_new,
-                                           int64_t *__restrict__ new_off) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t > v_new) return;
-  new_off[t] = old_off[t < v_old ? t : v_old] + delta_off[t];
-}
-
-// largest t in [a, b] with off[t] <= p; the caller guarantees off[a] <= p < off[b + 1]
-__device__ inline int32_t bm25_term_at(const int64_t *__restrict__ off, int32_t a, int32_t b, int64_t p) {
-  while (a < b) {
-    const int32_t m = a + (b - a + 1) / 2;
-    if (off[m] <= p)
-      a = m;
-    else
-      b = m - 1;
-  }
-  return a;
-}
 
 struct AppTerm {  // where term t's postings lie: [begin, end) merged = n_old old ones from src_old, then the delta's
   int64_t begin, end, src_old, n_old, src_delta;
@@ -129,7 +107,7 @@ __global__ void bm25_append_live_kernel(uint32_t *__restrict__ bits, int64_t n_o
 namespace {
 
 // The shared device path: n_new > 0 documents (device arrays on `st`) after the h->ndocs > 0
-// existing ones.  Nothing of the handle changes before the swap below.
+// existing ones.
 int bm25_append_device(cm_bm25 *h, const int32_t *term_ids_dev, const int64_t *doc_off_dev, int64_t n_new,
                        int64_t ntokens, int32_t vocab, hipStream_t st) {
   const int64_t n0 = h->ndocs, n1 = n0 + n_new, p0 = h->npost;
@@ -143,45 +121,26 @@ int bm25_append_device(cm_bm25 *h, const int32_t *term_ids_dev, const int64_t *d
     return rc;
   const int64_t p1 = p0 + dp;
   const int64_t w0 = std::max<int64_t>(1, ceil_div(n0, 32)), w1 = ceil_div(n1, 32);
-  TmpBuf f_off, f_doc, f_tf, f_pos, f_dl, f_live;  // the fresh arrays; after the swap, the old ones
-  if ((rc = f_off.ensure(((size_t)vocab + 1) * 8)) || (rc = f_doc.ensure((size_t)std::max<int64_t>(p1, 1) * 4)) ||
-      (rc = f_tf.ensure((size_t)std::max<int64_t>(p1, 1) * 2)) ||
-      (rc = f_pos.ensure((size_t)std::max<int64_t>(p1, 1) * 4)) || (rc = f_dl.ensure((size_t)n1 * 4)) ||
-      (rc = f_live.ensure((size_t)w1 * 4)))
+  FreshArrays f;
+  if ((rc = bm25_fresh_alloc(f, vocab, p1, n1)) || (rc = bm25_fresh_offsets(h, f, vocab, nullptr, d_off.as<int64_t>(), st)))
     return rc;
-  hipLaunchKernelGGL(bm25_append_offsets_kernel, dim3((unsigned)ceil_div((int64_t)vocab + 1, 256)), dim3(256), 0, st,
-                     h->term_off.as<int64_t>(), v0, d_off.as<int64_t>(), vocab, f_off.as<int64_t>());
-  CM_HIP(hipGetLastError());
   if (p1 > 0) {
     h->timer.begin(st);  // cm_bm25_timing: the merge kernel alone
     hipLaunchKernelGGL(bm25_append_merge_kernel, dim3((unsigned)ceil_div(p1, kAppChunk)), dim3(kAppThreads), 0, st,
-                       f_off.as<int64_t>(), h->term_off.as<int64_t>(), d_off.as<int64_t>(), v0, vocab, p1,
+                       f.off.as<int64_t>(), h->term_off.as<int64_t>(), d_off.as<int64_t>(), v0, vocab, p1,
                        h->post_doc.as<int32_t>(), h->post_tf.as<uint16_t>(), h->post_pos.as<uint32_t>(),
-                       d_doc.as<int32_t>(), d_tf.as<uint16_t>(), d_pos.as<uint32_t>(), f_doc.as<int32_t>(),
-                       f_tf.as<uint16_t>(), f_pos.as<uint32_t>());
+                       d_doc.as<int32_t>(), d_tf.as<uint16_t>(), d_pos.as<uint32_t>(), f.doc.as<int32_t>(),
+                       f.tf.as<uint16_t>(), f.pos.as<uint32_t>());
     h->timer.end(st);
     CM_HIP(hipGetLastError());
   }
-  CM_HIP(hipMemcpyAsync(f_dl.ptr, h->dl.ptr, (size_t)n0 * 4, hipMemcpyDeviceToDevice, st));
-  CM_HIP(hipMemcpyAsync(f_dl.as<int32_t>() + n0, d_dl.ptr, (size_t)n_new * 4, hipMemcpyDeviceToDevice, st));
-  CM_HIP(hipMemcpyAsync(f_live.ptr, h->live.ptr, (size_t)w0 * 4, hipMemcpyDeviceToDevice, st));
+  CM_HIP(hipMemcpyAsync(f.dl.ptr, h->dl.ptr, (size_t)n0 * 4, hipMemcpyDeviceToDevice, st));
+  CM_HIP(hipMemcpyAsync(f.dl.as<int32_t>() + n0, d_dl.ptr, (size_t)n_new * 4, hipMemcpyDeviceToDevice, st));
+  CM_HIP(hipMemcpyAsync(f.live.ptr, h->live.ptr, (size_t)w0 * 4, hipMemcpyDeviceToDevice, st));
   hipLaunchKernelGGL(bm25_append_live_kernel, dim3((unsigned)ceil_div(w1 - (n0 >> 5), 256)), dim3(256), 0, st,
-                     f_live.as<uint32_t>(), n0, n1);
+                     f.live.as<uint32_t>(), n0, n1);
   CM_HIP(hipGetLastError());
-  CM_HIP(hipStreamSynchronize(st));
-  swap_buf(h->term_off, f_off);
-  swap_buf(h->post_doc, f_doc);
-  swap_buf(h->post_tf, f_tf);
-  swap_buf(h->post_pos, f_pos);
-  swap_buf(h->dl, f_dl);
-  swap_buf(h->live, f_live);
-  h->ndocs = n1;
-  h->npost = p1;
-  h->vocab = vocab;
-  h->n_live = h->own_live += n_new;  // (installed statistics give way to the index's own, as after a build)
-  h->sum_len = h->own_len += ntokens;
-  if (h->log_n >= 0 && (rc = bm25_grow_logtab(h, n1))) return rc;
-  return bm25_finish_build(h, st);
+  return bm25_install(h, f, n1, p1, vocab, n_new, ntokens, st);
 }
 
 // the checks both forms share; *done: nothing (more) to do, return rc
@@ -222,12 +181,8 @@ int cm_bm25_append(cm_bm25 *h, const int32_t *term_ids, const int64_t *doc_off, 
   if (done) return rc;
   if (!doc_off) CM_FAIL(CM_EINVAL, "doc_off is NULL");
   if (doc_off[0] != 0) CM_FAIL(CM_EINVAL, "doc_off must start at 0");
-  for (int64_t d = 0; d < n_new; ++d)
-    if (doc_off[d + 1] < doc_off[d]) CM_FAIL(CM_EINVAL, "doc_off must be non-decreasing");
-  const int64_t ntok = doc_off[n_new];
-  if (ntok > 0 && !term_ids) CM_FAIL(CM_EINVAL, "term_ids is NULL");
-  for (int64_t p = 0; p < ntok; ++p)
-    if (term_ids[p] < 0 || term_ids[p] >= vocab) CM_FAIL(CM_EINVAL, "term id out of range");
+  const int64_t ntok = bm25_checked_ntok(term_ids, doc_off, n_new, vocab);
+  if (ntok < 0) return CM_EINVAL;
   DeviceGuard dg(h->dev);
   if (h->ndocs == 0) {
     if ((rc = cm_bm25_build(h, term_ids, doc_off, n_new, vocab, nullptr)) && rc != CM_EZERODIV) return rc;

@@ -15,18 +15,13 @@
 //           position at sbase + popc(lower survivors); a wave's survivors are consecutive.
 // Two passes with a scan between them, not one pass with a look-back between workgroups: no
 // workgroup ever waits for another, stream order is the only synchronisation.  The price is a
-// second read of post_doc.  The fresh arrays replace the old ones only after everything that can
-// fail on the way has not; K7's second half (bm25_finish_build) then recomputes df, the idf table
-// and the head tiles as a build does.
+// second read of post_doc.  Pass A, the offsets and the steps around them are the plan all three
+// mutations share: cm_bm25_mutate.inc.
 //
 // Peak device memory: old + new postings (10 B each) plus 16 B per 64 postings (smask, sbase); the
 // old arrays are freed when the call returns.
 
 namespace cm {
-
-constexpr int kRmThreads = 256;
-constexpr int kRmGroups = 8;  // 64-posting groups per wave
-constexpr int64_t kRmChunk = (int64_t)(kRmThreads / 64) * kRmGroups * 64;  // postings per workgroup
 
 // One thread per 32 rows: keep word and its popcount (cnt[], scanned into the rank words by the
 // caller); tot[0] += removed rows that were live, tot[1] += their lengths (sum_len counts live
@@ -70,40 +65,6 @@ __global__ void __launch_bounds__(256) bm25_rm_keep_kernel(const uint32_t *__res
     if (n_gone) atomicAdd(&tot[0], n_gone);
     if (len_gone) atomicAdd(&tot[1], len_gone);
   }
-}
-
-// Pass A: smask[g] = survivors among postings [64 g, 64 g + 64), cnt[g] = their number.
-__global__ void __launch_bounds__(kRmThreads) bm25_rm_flag_kernel(const int32_t *__restrict__ post_doc, int64_t npost,
-                                                                  const uint32_t *__restrict__ keep,
-                                                                  unsigned long long *__restrict__ smask,
-                                                                  int64_t *__restrict__ cnt) {
-  const int lane = threadIdx.x & 63;
-  const int64_t g0 = ((int64_t)blockIdx.x * (kRmThreads / 64) + (threadIdx.x >> 6)) * kRmGroups;
-#pragma unroll
-  for (int u = 0; u < kRmGroups; ++u) {
-    const int64_t g = g0 + u, p = g * 64 + lane;  // (g is wave-uniform)
-    if (g * 64 >= npost) break;
-    bool s = false;
-    if (p < npost) {
-      const int32_t d = post_doc[p];
-      s = (keep[d >> 5] >> (d & 31)) & 1u;
-    }
-    const unsigned long long m = __ballot(s);
-    if (lane == 0) {
-      smask[g] = m;
-      cnt[g] = (int64_t)__popcll(m);
-    }
-  }
-}
-
-// term_off'[t] for t in [0, vocab]: the number of survivors before posting term_off[t].
-__global__ void bm25_rm_offsets_kernel(const int64_t *__restrict__ old_off, int32_t vocab, int64_t npost,
-                                       const unsigned long long *__restrict__ smask,
-                                       const int64_t *__restrict__ sbase, int64_t p1, int64_t *__restrict__ new_off) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t > vocab) return;
-  const int64_t p = old_off[t];
-  new_off[t] = p >= npost ? p1 : sbase[p >> 6] + (int64_t)__popcll(smask[p >> 6] & ((1ull << (p & 63)) - 1ull));
 }
 
 // Pass B: the survivors of group g go to out[sbase[g] ...), in order, with their new row numbers.
@@ -159,7 +120,7 @@ __global__ void bm25_rm_rows_kernel(const uint32_t *__restrict__ keep, const int
 namespace {
 
 // The shared device path: h->ndocs > 0 rows, remove_bits_dev (ceil(ndocs / 32) words) readable on
-// `st`.  Nothing of the handle changes before the swap below.
+// `st`.
 int bm25_remove_device(cm_bm25 *h, const uint32_t *remove_bits_dev, hipStream_t st) {
   const int64_t n0 = h->ndocs, p0 = h->npost, nw = ceil_div(n0, 32);
   const int32_t vocab = h->vocab;
@@ -176,12 +137,7 @@ int bm25_remove_device(cm_bm25 *h, const uint32_t *remove_bits_dev, hipStream_t 
                      h->live.as<uint32_t>(), h->dl.as<int32_t>(), n0, nw, keep.as<uint32_t>(), cnt.as<int32_t>(),
                      tot.as<unsigned long long>());
   CM_HIP(hipGetLastError());
-  {
-    size_t need = 0;
-    CM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, cnt.as<int32_t>(), rank_w.as<int32_t>(), nw + 1, st));
-    if ((rc = cub_tmp.ensure(need))) return rc;
-    CM_HIP(hipcub::DeviceScan::ExclusiveSum(cub_tmp.ptr, need, cnt.as<int32_t>(), rank_w.as<int32_t>(), nw + 1, st));
-  }
+  if ((rc = bm25_exclusive_sum(cub_tmp, cnt.as<int32_t>(), rank_w.as<int32_t>(), nw + 1, st))) return rc;
   int32_t n1_32 = 0;
   int64_t gone[2] = {0, 0};  // removed rows that were live, their lengths
   CM_HIP(hipMemcpyAsync(&n1_32, rank_w.as<int32_t>() + nw, 4, hipMemcpyDeviceToHost, st));
@@ -190,69 +146,28 @@ int bm25_remove_device(cm_bm25 *h, const uint32_t *remove_bits_dev, hipStream_t 
   const int64_t n1 = n1_32;
   if (n1 == n0) return CM_OK;  // no bit set below ndocs
   if (n1 == 0) return cm_bm25_build(h, nullptr, nullptr, 0, vocab, nullptr);  // every document: the build of none
-  // -- pass A and the scan: which postings survive, and where each group of 64 goes
-  const int64_t ng = ceil_div(p0, 64);
-  TmpBuf smask, sbase;
-  int64_t p1 = 0;
+  // -- pass A and the scan: which postings survive, and where each group of 64 goes (cm_bm25_timing:
+  // pass A with its scan, then pass B, one pair each)
+  Survivors s;
+  if ((rc = bm25_survivor_pass(h, keep.as<uint32_t>(), cub_tmp, s, st))) return rc;
+  const int64_t p1 = s.n;
+  FreshArrays f;
+  if ((rc = bm25_fresh_alloc(f, vocab, p1, n1)) || (rc = bm25_fresh_offsets(h, f, vocab, &s, nullptr, st))) return rc;
   if (p0 > 0) {
-    if ((rc = smask.ensure((size_t)ng * 8)) || (rc = sbase.ensure(((size_t)ng + 1) * 8))) return rc;
-    CM_HIP(hipMemsetAsync(sbase.as<int64_t>() + ng, 0, 8, st));
-    h->timer.begin(st);  // cm_bm25_timing: pass A with its scan, then pass B, one pair each
-    hipLaunchKernelGGL(bm25_rm_flag_kernel, dim3((unsigned)ceil_div(p0, kRmChunk)), dim3(kRmThreads), 0, st,
-                       h->post_doc.as<int32_t>(), p0, keep.as<uint32_t>(), smask.as<unsigned long long>(),
-                       sbase.as<int64_t>());
-    CM_HIP(hipGetLastError());
-    size_t need = 0;
-    CM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, sbase.as<int64_t>(), sbase.as<int64_t>(), ng + 1, st));
-    if (need > cub_tmp.bytes) {
-      cub_tmp.release();
-      if ((rc = cub_tmp.ensure(need))) return rc;
-    }
-    CM_HIP(hipcub::DeviceScan::ExclusiveSum(cub_tmp.ptr, need, sbase.as<int64_t>(), sbase.as<int64_t>(), ng + 1, st));
-    h->timer.end(st);
-    CM_HIP(hipMemcpyAsync(&p1, sbase.as<int64_t>() + ng, 8, hipMemcpyDeviceToHost, st));
-    CM_HIP(hipStreamSynchronize(st));
-  }
-  // -- the fresh arrays; after the swap, the old ones
-  const int64_t w1 = ceil_div(n1, 32);
-  TmpBuf f_off, f_doc, f_tf, f_pos, f_dl, f_live;
-  if ((rc = f_off.ensure(((size_t)vocab + 1) * 8)) || (rc = f_doc.ensure((size_t)std::max<int64_t>(p1, 1) * 4)) ||
-      (rc = f_tf.ensure((size_t)std::max<int64_t>(p1, 1) * 2)) ||
-      (rc = f_pos.ensure((size_t)std::max<int64_t>(p1, 1) * 4)) || (rc = f_dl.ensure((size_t)n1 * 4)) ||
-      (rc = f_live.ensure((size_t)w1 * 4)))
-    return rc;
-  if (p0 > 0) {
-    hipLaunchKernelGGL(bm25_rm_offsets_kernel, dim3((unsigned)ceil_div((int64_t)vocab + 1, 256)), dim3(256), 0, st,
-                       h->term_off.as<int64_t>(), vocab, p0, smask.as<unsigned long long>(), sbase.as<int64_t>(), p1,
-                       f_off.as<int64_t>());
-    CM_HIP(hipGetLastError());
     h->timer.begin(st);
     hipLaunchKernelGGL(bm25_rm_compact_kernel, dim3((unsigned)ceil_div(p0, kRmChunk)), dim3(kRmThreads), 0, st,
                        h->post_doc.as<int32_t>(), h->post_tf.as<uint16_t>(), h->post_pos.as<uint32_t>(), p0,
-                       keep.as<uint32_t>(), rank_w.as<int32_t>(), smask.as<unsigned long long>(), sbase.as<int64_t>(),
-                       f_doc.as<int32_t>(), f_tf.as<uint16_t>(), f_pos.as<uint32_t>());
+                       keep.as<uint32_t>(), rank_w.as<int32_t>(), s.mask(), s.base(), f.doc.as<int32_t>(),
+                       f.tf.as<uint16_t>(), f.pos.as<uint32_t>());
     h->timer.end(st);
     CM_HIP(hipGetLastError());
-  } else {
-    CM_HIP(hipMemsetAsync(f_off.ptr, 0, ((size_t)vocab + 1) * 8, st));
   }
-  CM_HIP(hipMemsetAsync(f_live.ptr, 0, (size_t)w1 * 4, st));
+  CM_HIP(hipMemsetAsync(f.live.ptr, 0, (size_t)ceil_div(n1, 32) * 4, st));
   hipLaunchKernelGGL(bm25_rm_rows_kernel, dim3((unsigned)ceil_div(nw, 256)), dim3(256), 0, st, keep.as<uint32_t>(),
-                     rank_w.as<int32_t>(), h->live.as<uint32_t>(), h->dl.as<int32_t>(), nw, f_dl.as<int32_t>(),
-                     f_live.as<uint32_t>());
+                     rank_w.as<int32_t>(), h->live.as<uint32_t>(), h->dl.as<int32_t>(), nw, f.dl.as<int32_t>(),
+                     f.live.as<uint32_t>());
   CM_HIP(hipGetLastError());
-  CM_HIP(hipStreamSynchronize(st));
-  swap_buf(h->term_off, f_off);
-  swap_buf(h->post_doc, f_doc);
-  swap_buf(h->post_tf, f_tf);
-  swap_buf(h->post_pos, f_pos);
-  swap_buf(h->dl, f_dl);
-  swap_buf(h->live, f_live);
-  h->ndocs = n1;
-  h->npost = p1;
-  h->n_live = h->own_live -= gone[0];  // (installed statistics give way to the index's own, as after a build)
-  h->sum_len = h->own_len -= gone[1];
-  return bm25_finish_build(h, st);
+  return bm25_install(h, f, n1, p1, vocab, -gone[0], -gone[1], st);
 }
 
 }  // namespace
@@ -272,15 +187,13 @@ int cm_bm25_remove(cm_bm25 *h, const int64_t *rows, int64_t n_rows) {
   if (n_rows < 0) CM_FAIL(CM_EINVAL, "n_rows must be >= 0");
   if (n_rows == 0) return CM_OK;
   if (!rows) CM_FAIL(CM_EINVAL, "rows is NULL");
-  for (int64_t i = 0; i < n_rows; ++i)
-    if (rows[i] < 0 || rows[i] >= h->ndocs) CM_FAIL(CM_EINVAL, "row out of range");
-  std::vector<uint32_t> bits((size_t)ceil_div(h->ndocs, 32), 0u);
-  for (int64_t i = 0; i < n_rows; ++i) bits[(size_t)(rows[i] >> 5)] |= 1u << (rows[i] & 31);
+  std::vector<uint32_t> bits;
+  int rc = bm25_rows_to_bits(rows, n_rows, h->ndocs, false, bits);
+  if (rc) return rc;
   DeviceGuard dg(h->dev);
   // only the bitmap goes up; the rest is the device path
   TmpBuf up;
-  int rc = up.ensure(bits.size() * 4);
-  if (rc) return rc;
+  if ((rc = up.ensure(bits.size() * 4))) return rc;
   CM_HIP(hipMemcpyAsync(up.ptr, bits.data(), bits.size() * 4, hipMemcpyHostToDevice, h->stream));
   return bm25_remove_device(h, up.as<uint32_t>(), h->stream);
 }

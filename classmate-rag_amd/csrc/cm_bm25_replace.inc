@@ -1,5 +1,5 @@
 // cm_bm25_replace / cm_bm25_replace_dev: documents replaced in place without a rebuild (included by
-// cm_bm25.hip, after cm_bm25_append.inc and cm_bm25_remove.inc, whose kernels it reuses).
+// cm_bm25.hip, after cm_bm25_remove.inc, whose keep-word kernel it reuses).
 //
 // A replaced document keeps its row, so no row is renumbered: the new CSR is the old one without
 // the replaced rows' postings, merged term by term with the delta CSR of the replacement texts.
@@ -20,8 +20,8 @@
 //           me + delta postings of t before me" for either kind: the two kernels write every slot
 //           of [0, p_surv + dp) exactly once.  No merge path, no look-back between workgroups.
 //   rows    dl' = dl with d_dl[i] at rows[i]; live' = live | R.
-// The fresh arrays replace the old ones only after everything that can fail on the way has not;
-// K7's second half (bm25_finish_build) then recomputes df, the idf table and the head tiles.
+// Pass A, the offsets and the steps around them are the plan all three mutations share:
+// cm_bm25_mutate.inc.
 //
 // Peak device memory: old + new postings (10 B each), 16 B per 64 postings (smask, sbase), the
 // delta and its sort scratch.
@@ -41,24 +41,6 @@ __global__ void bm25_rp_rows_check_kernel(const int64_t *__restrict__ rows, int6
   }
   if (i > 0 && rows[i - 1] >= r) atomicOr(bad, 1);
   if (bits) atomicOr(&bits[r >> 5], 1u << (r & 31));
-}
-
-// the number of old postings that survive before old posting p (p <= npost)
-__device__ inline int64_t bm25_rp_surv(int64_t p, int64_t npost, int64_t p_surv,
-                                       const unsigned long long *__restrict__ smask,
-                                       const int64_t *__restrict__ sbase) {
-  return p >= npost ? p_surv : sbase[p >> 6] + (int64_t)__popcll(smask[p >> 6] & ((1ull << (p & 63)) - 1ull));
-}
-
-// term_off'[t] for t in [0, v_new]
-__global__ void bm25_rp_offsets_kernel(const int64_t *__restrict__ old_off, int32_t v_old,
-                                       const int64_t *__restrict__ d_off, int32_t v_new, int64_t npost,
-                                       const unsigned long long *__restrict__ smask,
-                                       const int64_t *__restrict__ sbase, int64_t p_surv,
-                                       int64_t *__restrict__ new_off) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t > v_new) return;
-  new_off[t] = bm25_rp_surv(old_off[t < v_old ? t : v_old], npost, p_surv, smask, sbase) + d_off[t];
 }
 
 // first j in [a, b) with rows[d_doc[j]] >= d (b when none): the delta postings of one term before row d
@@ -154,7 +136,7 @@ __global__ void __launch_bounds__(256) bm25_rp_scatter_delta_kernel(
     else
       b = mid;
   }
-  const int64_t q = j + bm25_rp_surv(a, npost, p_surv, smask, sbase);
+  const int64_t q = j + bm25_surv(a, npost, p_surv, smask, sbase);
   out_doc[q] = d;
   out_tf[q] = d_tf[j];
   out_pos[q] = d_pos[j];
@@ -180,7 +162,6 @@ namespace {
 
 // The shared device path: n_rows > 0 rows (ascending, distinct, in range: checked by the caller)
 // with their bitmap, the replacement documents' tokens, all readable on `st`; h->ndocs > 0.
-// Nothing of the handle changes before the swap below.
 int bm25_replace_device(cm_bm25 *h, const int64_t *rows_dev, const uint32_t *repl_bits_dev, int64_t n_rows,
                         const int32_t *term_ids_dev, const int64_t *doc_off_dev, int64_t ntokens, int32_t vocab,
                         hipStream_t st) {
@@ -202,80 +183,44 @@ int bm25_replace_device(cm_bm25 *h, const int64_t *rows_dev, const uint32_t *rep
                      h->live.as<uint32_t>(), h->dl.as<int32_t>(), n0, nw, keep.as<uint32_t>(), cnt.as<int32_t>(),
                      tot.as<unsigned long long>());
   CM_HIP(hipGetLastError());
-  // -- pass A and the scan: which old postings survive, and how many before each group of 64
-  const int64_t ng = ceil_div(p0, 64);
-  TmpBuf smask, sbase;
-  int64_t p_surv = 0;
-  if (p0 > 0) {
-    if ((rc = smask.ensure((size_t)ng * 8)) || (rc = sbase.ensure(((size_t)ng + 1) * 8))) return rc;
-    CM_HIP(hipMemsetAsync(sbase.as<int64_t>() + ng, 0, 8, st));
-    h->timer.begin(st);  // cm_bm25_timing: pass A with its scan, then the two scatters, one pair each
-    hipLaunchKernelGGL(bm25_rm_flag_kernel, dim3((unsigned)ceil_div(p0, kRmChunk)), dim3(kRmThreads), 0, st,
-                       h->post_doc.as<int32_t>(), p0, keep.as<uint32_t>(), smask.as<unsigned long long>(),
-                       sbase.as<int64_t>());
-    CM_HIP(hipGetLastError());
-    size_t need = 0;
-    CM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, sbase.as<int64_t>(), sbase.as<int64_t>(), ng + 1, st));
-    if ((rc = cub_tmp.ensure(need))) return rc;
-    CM_HIP(hipcub::DeviceScan::ExclusiveSum(cub_tmp.ptr, need, sbase.as<int64_t>(), sbase.as<int64_t>(), ng + 1, st));
-    h->timer.end(st);
-    CM_HIP(hipMemcpyAsync(&p_surv, sbase.as<int64_t>() + ng, 8, hipMemcpyDeviceToHost, st));
-  }
   int64_t gone[2] = {0, 0};  // replaced rows that were live, their lengths
   CM_HIP(hipMemcpyAsync(gone, tot.ptr, 16, hipMemcpyDeviceToHost, st));
   CM_HIP(hipStreamSynchronize(st));
-  // -- the fresh arrays; after the swap, the old ones
-  const int64_t p1 = p_surv + dp;
-  const int64_t w0 = std::max<int64_t>(1, nw);
-  TmpBuf f_off, f_doc, f_tf, f_pos, f_dl, f_live;
-  if ((rc = f_off.ensure(((size_t)vocab + 1) * 8)) || (rc = f_doc.ensure((size_t)std::max<int64_t>(p1, 1) * 4)) ||
-      (rc = f_tf.ensure((size_t)std::max<int64_t>(p1, 1) * 2)) ||
-      (rc = f_pos.ensure((size_t)std::max<int64_t>(p1, 1) * 4)) || (rc = f_dl.ensure((size_t)n0 * 4)) ||
-      (rc = f_live.ensure((size_t)w0 * 4)))
+  // -- pass A and the scan: which old postings survive, and how many before each group of 64
+  // (cm_bm25_timing: pass A with its scan, then the two scatters, one pair each)
+  Survivors s;
+  if ((rc = bm25_survivor_pass(h, keep.as<uint32_t>(), cub_tmp, s, st))) return rc;
+  const int64_t p_surv = s.n, p1 = p_surv + dp;
+  FreshArrays f;
+  if ((rc = bm25_fresh_alloc(f, vocab, p1, n0)) || (rc = bm25_fresh_offsets(h, f, vocab, &s, d_off.as<int64_t>(), st)))
     return rc;
-  hipLaunchKernelGGL(bm25_rp_offsets_kernel, dim3((unsigned)ceil_div((int64_t)vocab + 1, 256)), dim3(256), 0, st,
-                     h->term_off.as<int64_t>(), v0, d_off.as<int64_t>(), vocab, p0, smask.as<unsigned long long>(),
-                     sbase.as<int64_t>(), p_surv, f_off.as<int64_t>());
-  CM_HIP(hipGetLastError());
   if (p1 > 0) {
     h->timer.begin(st);
     if (p_surv > 0) {
       hipLaunchKernelGGL(bm25_rp_scatter_old_kernel, dim3((unsigned)ceil_div(p0, kRmChunk)), dim3(kRmThreads), 0, st,
                          h->term_off.as<int64_t>(), v0, h->post_doc.as<int32_t>(), h->post_tf.as<uint16_t>(),
-                         h->post_pos.as<uint32_t>(), p0, smask.as<unsigned long long>(), sbase.as<int64_t>(),
-                         d_off.as<int64_t>(), d_doc.as<int32_t>(), rows_dev, f_doc.as<int32_t>(),
-                         f_tf.as<uint16_t>(), f_pos.as<uint32_t>());
+                         h->post_pos.as<uint32_t>(), p0, s.mask(), s.base(), d_off.as<int64_t>(), d_doc.as<int32_t>(),
+                         rows_dev, f.doc.as<int32_t>(), f.tf.as<uint16_t>(), f.pos.as<uint32_t>());
       CM_HIP(hipGetLastError());
     }
     if (dp > 0) {
       hipLaunchKernelGGL(bm25_rp_scatter_delta_kernel, dim3((unsigned)ceil_div(dp, 256)), dim3(256), 0, st,
                          d_off.as<int64_t>(), vocab, d_doc.as<int32_t>(), d_tf.as<uint16_t>(), d_pos.as<uint32_t>(),
                          dp, rows_dev, h->term_off.as<int64_t>(), v0, h->post_doc.as<int32_t>(), p0,
-                         smask.as<unsigned long long>(), sbase.as<int64_t>(), p_surv, f_doc.as<int32_t>(),
-                         f_tf.as<uint16_t>(), f_pos.as<uint32_t>());
+                         s.mask(), s.base(), p_surv, f.doc.as<int32_t>(), f.tf.as<uint16_t>(),
+                         f.pos.as<uint32_t>());
       CM_HIP(hipGetLastError());
     }
     h->timer.end(st);
   }
-  CM_HIP(hipMemcpyAsync(f_dl.ptr, h->dl.ptr, (size_t)n0 * 4, hipMemcpyDeviceToDevice, st));
+  CM_HIP(hipMemcpyAsync(f.dl.ptr, h->dl.ptr, (size_t)n0 * 4, hipMemcpyDeviceToDevice, st));
   hipLaunchKernelGGL(bm25_rp_dl_kernel, dim3((unsigned)ceil_div(n_rows, 256)), dim3(256), 0, st, rows_dev,
-                     d_dl.as<int32_t>(), n_rows, f_dl.as<int32_t>());
+                     d_dl.as<int32_t>(), n_rows, f.dl.as<int32_t>());
   CM_HIP(hipGetLastError());
   hipLaunchKernelGGL(bm25_rp_live_kernel, dim3((unsigned)ceil_div(nw, 256)), dim3(256), 0, st, h->live.as<uint32_t>(),
-                     repl_bits_dev, nw, f_live.as<uint32_t>());
+                     repl_bits_dev, nw, f.live.as<uint32_t>());
   CM_HIP(hipGetLastError());
-  CM_HIP(hipStreamSynchronize(st));
-  swap_buf(h->term_off, f_off);
-  swap_buf(h->post_doc, f_doc);
-  swap_buf(h->post_tf, f_tf);
-  swap_buf(h->post_pos, f_pos);
-  swap_buf(h->dl, f_dl);
-  swap_buf(h->live, f_live);
-  h->npost = p1;
-  h->vocab = vocab;
-  h->n_live = h->own_live += n_rows - gone[0];  // (installed statistics give way to the index's own, as after a build)
-  h->sum_len = h->own_len += ntokens - gone[1];
-  return bm25_finish_build(h, st);
+  return bm25_install(h, f, n0, p1, vocab, n_rows - gone[0], ntokens - gone[1], st);
 }
 
 // the checks both forms share; *done: nothing (more) to do, return rc
@@ -326,19 +271,10 @@ int cm_bm25_replace(cm_bm25 *h, const int64_t *rows, int64_t n_rows, const int32
   if (!rows) CM_FAIL(CM_EINVAL, "rows is NULL");
   if (!doc_off) CM_FAIL(CM_EINVAL, "doc_off is NULL");
   if (doc_off[0] != 0) CM_FAIL(CM_EINVAL, "doc_off must start at 0");
-  for (int64_t d = 0; d < n_rows; ++d)
-    if (doc_off[d + 1] < doc_off[d]) CM_FAIL(CM_EINVAL, "doc_off must be non-decreasing");
-  const int64_t ntok = doc_off[n_rows];
-  if (ntok > 0 && !term_ids) CM_FAIL(CM_EINVAL, "term_ids is NULL");
-  for (int64_t p = 0; p < ntok; ++p)
-    if (term_ids[p] < 0 || term_ids[p] >= vocab) CM_FAIL(CM_EINVAL, "term id out of range");
-  std::vector<uint32_t> bits((size_t)ceil_div(h->ndocs, 32), 0u);
-  for (int64_t i = 0; i < n_rows; ++i) {
-    if (rows[i] < 0 || rows[i] >= h->ndocs) CM_FAIL(CM_EINVAL, "row out of range");
-    uint32_t &w = bits[(size_t)(rows[i] >> 5)];
-    if (w & (1u << (rows[i] & 31))) CM_FAIL(CM_EINVAL, "duplicate row");
-    w |= 1u << (rows[i] & 31);
-  }
+  const int64_t ntok = bm25_checked_ntok(term_ids, doc_off, n_rows, vocab);
+  if (ntok < 0) return CM_EINVAL;
+  std::vector<uint32_t> bits;
+  if ((rc = bm25_rows_to_bits(rows, n_rows, h->ndocs, true, bits))) return rc;
   // the documents in row order: sorted rows, their tokens and offsets
   std::vector<int64_t> order((size_t)n_rows), srows((size_t)n_rows), soff((size_t)n_rows + 1, 0);
   for (int64_t i = 0; i < n_rows; ++i) order[(size_t)i] = i;

@@ -443,6 +443,122 @@ def test_replacing_every_text_by_an_empty_one_raises_with_that_state(eng):
     assert (b.export()["dl"] == 0).all()             # (ref's wrapper never learnt its vocabulary: not exported)
 
 
+# ---- the edges of what append, remove and replace share (offsets kernel, survivor pass, install) ----
+# These cases exercise cm_bm25_remove and cm_bm25_append as well as the replace; they live here because
+# this file's helpers already cover all three calls (tests/test_gpu_bm25_remove.py and _append.py hold
+# each call's own cases).
+VS, VS2 = 300, 320                       # a small vocabulary, so that one term's run crosses a 64-group
+# old posting counts: a multiple of 64 below one workgroup's 2048, then one either side of 2048
+EDGE_POSTINGS = (1984, 2047, 2048, 2049)
+EDGE_ROWS = [0, 13, 38, 39]              # the first and the last document among them
+
+
+def _edge_docs(p0: int, seed: int = 3):
+    """40 documents of distinct terms below VS (one posting per token) with exactly p0 postings, and
+    replacement texts for EDGE_ROWS that use terms at and beyond VS.  Checked here for the seed in
+    use: some term behind the first starts its postings at the first slot of a 64-group."""
+    rng = np.random.default_rng(seed)
+    docs = [rng.choice(VS, size=k, replace=False).astype(np.int32) for k in [50] * 39 + [p0 - 39 * 50]]
+    fresh = [rng.choice(VS2, size=60, replace=False).astype(np.int32) for _ in EDGE_ROWS]
+    fresh[0] = np.union1d(fresh[0], [VS, VS2 - 1]).astype(np.int32)
+    off = np.concatenate([[0], np.cumsum(np.bincount(np.concatenate(docs), minlength=VS))])
+    assert off[-1] == p0
+    assert any(off[t] % 64 == 0 and off[t] < off[t + 1] for t in range(1, VS))
+    return docs, fresh
+
+
+def _edge_queries():
+    rng = np.random.default_rng(4)
+    return [[int(x) for x in rng.integers(0, VS2, 6)] + [VS, -1] for _ in range(8)]
+
+
+@pytest.mark.parametrize("p0", EDGE_POSTINGS)
+def test_posting_count_edges_equal_build(eng, p0):
+    docs, fresh = _edge_docs(p0)
+    allow_mask = np.arange(40) % 3 != 1
+    qs = _edge_queries()
+
+    def built(texts, vocab):
+        ref = eng.BM25Index()
+        ref.build(*_csr(texts), vocab)
+        ref.prepare_filtered()
+        return ref
+
+    b = built(docs, VS2)
+    assert b.num_postings == p0
+    b.remove(EDGE_ROWS)
+    ref = built([t for d, t in enumerate(docs) if d not in EDGE_ROWS], VS2)
+    _same_state(_state(b), _state(ref))
+    _same_searches(_searches(b, qs, allow_mask[:36]), _searches(ref, qs, allow_mask[:36]))
+
+    b = built(docs, VS)                              # the replacement brings the terms from VS on
+    assert b.num_postings == p0
+    b.replace(EDGE_ROWS, *_csr(fresh), VS2)
+    sub = list(docs)
+    for r, t in zip(EDGE_ROWS, fresh):
+        sub[r] = t
+    ref = built(sub, VS2)
+    _same_state(_state(b), _state(ref))
+    _same_searches(_searches(b, qs, allow_mask), _searches(ref, qs, allow_mask))
+
+
+def test_mutations_of_a_tombstoned_index_without_postings(eng):
+    """Documents present, none live: no posting to flag, scan or move (all-zero offsets)."""
+    docs, fresh = _edge_docs(1984)
+    b = eng.BM25Index()
+    b.build(*_csr(docs), VS, np.zeros(40, np.uint8))
+    assert b.num_docs == 40 and b.num_postings == 0
+    b.remove([0, 31, 32, 39])
+    kept = [t for d, t in enumerate(docs) if d not in (0, 31, 32, 39)]
+    ref = eng.BM25Index()
+    ref.build(*_csr(kept), VS, np.zeros(36, np.uint8))
+    assert b.num_docs == 36 and b.num_postings == 0
+    _same_state(_state(b), _state(ref))
+    b.replace([5], *_csr(fresh[:1]), VS2)            # ... and a replacement makes its row live
+    kept[5] = fresh[0]
+    live = np.zeros(36, np.uint8)
+    live[5] = 1
+    ref.build(*_csr(kept), VS2, live)
+    assert b.num_postings == fresh[0].shape[0]
+    _same_state(_state(b), _state(ref))
+
+
+def test_chained_mutations_with_filtered_searches_between(eng, queries):
+    """Append, remove, replace and append again on one handle whose filtered-search table was
+    prepared once, before the first: every search entry point after each step, against a build."""
+    docs, _, _ = make_docs(420, seed=33)
+    fresh = _draw(np.random.default_rng(34), _zipf(), 8, empty_mod=6)
+    fresh[0] = np.concatenate([fresh[0], np.array([NEW, V + 1], np.int32)])
+    b = eng.BM25Index()
+    b.build(*_csr(docs[:300]), V)
+    b.prepare_filtered()                             # the log table is for 300 documents
+    cur = list(docs[:300])
+
+    def check():
+        ref = eng.BM25Index()
+        ref.build(*_csr(cur), V2)
+        ref.prepare_filtered()
+        allow_mask = np.arange(len(cur)) % 3 != 1
+        _same_state(_state(b), _state(ref))
+        _same_searches(_searches(b, queries, allow_mask), _searches(ref, queries, allow_mask))
+
+    b.append(*_csr(docs[300:400]), V2)               # 400 documents: the table has to grow
+    cur += docs[300:400]
+    check()
+    gone = [0, 64, 299, 300, 399]
+    b.remove(gone)
+    cur[:] = [t for r, t in enumerate(cur) if r not in gone]
+    check()
+    rows = [0, 1, 63, 64, 200, 297, 298, 394]
+    b.replace(rows, *_csr(fresh), V2)
+    for r, t in zip(rows, fresh):
+        cur[r] = t
+    check()
+    b.append(*_csr(docs[400:]), V2)                  # 415 documents: beyond the table once more
+    cur += docs[400:]
+    check()
+
+
 # ---- BM25Store -------------------------------------------------------------------------------
 def _store_corpus():
     from synth import make_corpus, make_queries
