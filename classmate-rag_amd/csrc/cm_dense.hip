@@ -380,14 +380,6 @@ __global__ void __launch_bounds__(256) dense_prep_planes(const float *__restrict
   }
 }
 
-// Waves per K1c workgroup.  4 (one per SIMD) is the measured best: 8 (two per SIMD, 32 queries
-// each, 256 VGPRs with 16 spilled at tile boundaries) ran 5.63 vs 4.96 ms on the 10M x 768 scan --
-// the second wave did not hide barrier/epilogue time.  Kept selectable for experiments.
-#ifndef K1C_WAVES
-#define K1C_WAVES 4
-#endif
-constexpr int kK1cWaves = K1C_WAVES;
-
 // K1c/K1s per-query error bound E (see dense_rerank_kernel).
 __device__ inline float coarse_err(const float *qnorm, int qi, const float *row_norms, int dim) {
   const float qh = qnorm[4 * qi + 1], qlo = qnorm[4 * qi + 2];
@@ -395,33 +387,17 @@ __device__ inline float coarse_err(const float *qnorm, int qi, const float *row_
   return (qlo * mxh + mxl * qh + mxl * qlo + (float)dim * 5.9604645e-8f * mxh * qh + 2e-6f) * 1.001f;
 }
 
-#ifndef K1C_RING
-#define K1C_RING 8
-#endif
-constexpr int kRRing = K1C_RING;  // LDS ring slots (8 KB each): kRRing - 1 chunks in flight per CU
-// LDS-resident query chunks of the whole-pass K1c at ld 768 (the rest stay in registers); the ring
-// and these share the 160 KiB: (kRRing + 4 kK1cNql) x 8 KiB
-#ifndef K1C_NQL
-#define K1C_NQL 3
-#endif
-// cache-policy bits of K1c's corpus DMA (2 = nt: streamed once)
-#ifndef K1C_AUX
-#define K1C_AUX 2
-#endif
-// 1: K1s streams the plane with non-temporal loads (read once): 10M x 768, B = 16 2.48 -> 2.22 ms
+constexpr int kRRing = 8;  // K1c's LDS ring slots (8 KB each): kRRing - 1 chunks in flight per CU
+// LDS-resident query chunks of K1c at ld 768 (the rest stay in registers); the ring and these
+// share the 160 KiB: (kRRing + 4 kK1cNql) x 8 KiB
+constexpr int kK1cNql = 3;
+// cache-policy bits of K1c's and K1q's corpus DMA (2 = nt: streamed once)
+constexpr int kK1cAux = 2;
+// K1s streams the plane with non-temporal loads (read once): 10M x 768, B = 16 2.48 -> 2.22 ms
 // (6.9 TB/s, 0.87 of the 8 TB/s peak)
-#ifndef K1S_NT
-#define K1S_NT 1
-#endif
+constexpr bool kK1sNt = true;
 // query chunks whose resident fragments are pinned to AGPRs (see the K1c prologue)
-#ifndef K1C_QAGPR
-#define K1C_QAGPR 8
-#endif
-// 1: the interleaved K1c chunk schedule (one non-MFMA step per MFMA); 0: the two-block schedule
-#ifndef K1C_SCHED
-#define K1C_SCHED 1
-#endif
-constexpr int kK1cNql = K1C_NQL;
+constexpr int kK1cQAgpr = 8;
 constexpr int kRRows = 64;      // rows per compute tile / chunk
 constexpr int kCBufCap = 64;    // candidate slots per (range, query)
 
@@ -456,9 +432,6 @@ __device__ __attribute__((always_inline)) inline void coarse_epilogue(const f32x
 #pragma unroll
         for (int r = 0; r < 4; ++r) mx = fmaxf(mx, acc[rt][qt][r]);
       if (__ballot(1.0f - mx <= sd[qt]) == 0) continue;  // no row of the tile under any seed
-#ifdef K1C_NOHIT
-      if (sd[qt] < 1e30f) continue;  // timing ablation only: never append
-#endif
       // Append every live row under the seed, position by position (static register indices):
       // one ballot per position tells which of the 64 lanes hit; the slot of a hit is the query's
       // running count plus the hits of the same query's lower lanes (g' < g) at this position --
@@ -493,73 +466,59 @@ __device__ inline uint32_t lane_live16(uint64_t tmask, int g) {
 
 // ---------------------------------------------------------------------------
 // K1c scan (coarse f16, Xh plane only), resident-query form for ld = 64 KC.
-// 64 W threads (W = kK1cWaves: 4 -> one wave per SIMD, 8 -> two); wave w owns queries 256w/W.. of
-// the 256-query pass and keeps their Qh fragments resident -- chunks 0..KC-NQL-1 in registers (32
-// VGPRs each), the last NQL chunks in LDS -- so the corpus is the only memory stream: 64-row x
-// 64-f16 chunks (8 KB = 8 fragment blocks; one glds wave-instruction = one 1 KB block) LDS-DMA'd
-// into a kRRing-slot ring, retired by a counted vmcnt and published by a raw s_barrier: no
-// vmcnt(0) and no query reloads in the loop.  The ring image is the plane's fragment-major block
-// order, read back lane-linearly (conflict-free).  Compute tiles are 64 rows.
+// One workgroup of 4 waves (one per SIMD) per (256-query pass, row range); wave w owns queries
+// 64w..64w+63 of the pass and keeps their Qh fragments resident -- chunks 0..KC-NQL-1 in registers
+// (32 VGPRs each), the last NQL chunks in LDS -- so the corpus is the only memory stream: 64-row x
+// 64-f16 chunks (8 KB = 8 fragment blocks; one glds wave-instruction = one 1 KB block, 2 per wave
+// and chunk) LDS-DMA'd into a kRRing-slot ring, retired by a counted vmcnt and published by a raw
+// s_barrier: no vmcnt(0) and no query reloads in the loop.  The ring image is the plane's
+// fragment-major block order, read back lane-linearly (conflict-free).  Compute tiles are 64 rows.
 //   MINONLY (sample pre-pass): per query, the minimum coarse distance over the workgroup's
 //     live+allowed rows -> out_min[pass][wg][q].
 //   main pass: every live+allowed row with coarse distance <= seed[q] is appended to the
 //     (range, query) candidate buffer out_keys[pass][wg][q][kCBufCap];
 //     out_cnt[pass][wg][q] = appended count (> kCBufCap: the buffer overflowed).
-template <int NQL, int RING = kRRing>
+// Instances: <12, kK1cNql> (ld 768) and <6, 0> (ld 384, every query chunk in registers), each
+// MINONLY or not.  Forms measured and removed (DESIGN.md "Removed dense scan variants"): 8 waves,
+// paired half passes with a 20-slot ring, the two-block chunk schedule.
+template <int NQL>
 struct K1rLds {
   static constexpr int ring = 0;
-  static constexpr int qf = ring + RING * 8192;            // [NQL][W waves][32/W frags][64 lanes] x 16 B
+  static constexpr int qf = ring + kRRing * 8192;          // [NQL][4 waves][8 frags][64 lanes] x 16 B
   static constexpr int total = qf + NQL * 4 * 8 * 1024;
 };
 
-//   QPASS = 128 (the paired form, K1c2): a workgroup holds half of the pass's queries, all in
-//     registers (no LDS-resident query chunks), so the whole 160 KiB LDS is the DMA ring (20 slots,
-//     >= 18 chunks = 144 KiB in flight per CU, deep enough to cover the loaded HBM latency); the
-//     two workgroups of a (pass, range) are blocks b and b + 8 -- one XCD under round-robin
-//     placement -- so the second reader of every chunk finds it in (or on its way into) that XCD's L2
-//     and the corpus still crosses HBM about once.  Placement is a speed assumption only.
-template <int KC, int NQL, bool MINONLY, int W, int RING = kRRing, int QPASS = kBQPass>
-__global__ void __launch_bounds__(64 * W, 1)
+template <int KC, int NQL, bool MINONLY>
+__global__ void __launch_bounds__(256, 1)
     dense_coarse_scan_kernel(const _Float16 *__restrict__ Xh, const uint32_t *__restrict__ live,
                              const uint32_t *__restrict__ allow, int64_t n_words, const _Float16 *__restrict__ Qh,
                              int nq, const float *__restrict__ seed, int64_t rows_per_wg, int64_t rows_end, int n_wg,
                              uint64_t *__restrict__ out_keys, uint32_t *__restrict__ out_cnt,
-                             float *__restrict__ out_min, int dbg) {
+                             float *__restrict__ out_min) {
   constexpr int ld = 64 * KC;
   constexpr int KR = KC - NQL;  // register-resident query chunks
-  using LL = K1rLds<NQL, RING>;
-  constexpr int QT = QPASS / (16 * W);  // 16-query tiles per wave
-  constexpr int NF = 2 * QT;            // query fragments per wave and chunk
-  constexpr int PCS = 8 / W;            // 1 KB DMA pieces per wave and chunk
-  constexpr int H = kBQPass / QPASS;    // workgroups per (pass, range)
-#if defined(K1C_DBG)
-  dbg = K1C_DBG;  // compile-time timing ablation (tools/build_dense_variant.sh), folds like the product
-#elif !defined(CM_ABLATION)
-  dbg = 0;  // product build: the ablation branches fold away (exact lgkmcnt / vmcnt counting)
-#endif
-  static_assert(W == 4 || W == 8, "K1c: 4 or 8 waves");
-  static_assert(LL::total <= 160 * 1024, "K1c: LDS ring + query chunks + mask exceed 160 KiB");
-  static_assert(H == 1 || H == 2, "K1c: full or half passes");
+  using LL = K1rLds<NQL>;
+  constexpr int W = 4;                    // waves
+  constexpr int RING = kRRing;
+  constexpr int QT = kBQPass / (16 * W);  // 16-query tiles per wave
+  constexpr int NF = 2 * QT;              // query fragments per wave and chunk
+  constexpr int PCS = 8 / W;              // 1 KB DMA pieces per wave and chunk
+  static_assert(KR > 0, "K1c: the first query chunk is register-resident");
+  static_assert(LL::total <= 160 * 1024, "K1c: LDS ring + query chunks exceed 160 KiB");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4;
   const int j = lane & 15;
-  int lr = blockIdx.x, half = 0;  // linear (pass, range) index and query half
-  if (H == 2) {                   // blocks b, b + 8 -> same (pass, range), halves 0 / 1
-    const int grp = blockIdx.x >> 3;
-    half = grp & 1;
-    lr = (grp >> 1) * 8 + (blockIdx.x & 7);
-  }
+  const int lr = blockIdx.x;  // linear (pass, range) index
   const int wg = lr % n_wg;
   const int qp = lr / n_wg;
-  if (H == 2 && qp * kBQPass >= nq) return;  // grid padding of the paired mapping (whole workgroup)
   const int64_t r_begin = (int64_t)wg * rows_per_wg;
   const int64_t r_end = min(r_begin + rows_per_wg, rows_end);
   const int ntiles = r_begin < r_end ? (int)((r_end - r_begin) / kRRows) : 0;
   const int total = ntiles * KC;
-  const int qc0 = half * QPASS + wave * 16 * QT;  // wave's first query within the pass
+  const int qc0 = wave * 16 * QT;  // wave's first query within the pass
   const int qg0 = qp * kBQPass + qc0;
 
   // resident query fragments (B operand): lane (g, j) of q-tile qt, chunk c, half sb holds
@@ -574,7 +533,7 @@ __global__ void __launch_bounds__(64 * W, 1)
     for (int qt = 0; qt < QT; ++qt)
 #pragma unroll
       for (int sb = 0; sb < 2; ++sb) qres[c][qt][sb] = *qsrc(c, qt, sb);
-  // pin the first K1C_QAGPR chunks' fragments to AGPRs (the 256 of them hold 8 chunks): the
+  // pin the first kK1cQAgpr chunks' fragments to AGPRs (the 256 of them hold 8 chunks): the
   // MFMA reads its B operand from an AGPR directly, where a VGPR value the allocator parked
   // in an AGPR is copied back before every use (16 v_accvgpr_read per chunk).  With the
   // accumulators in VGPRs (-mllvm -amdgpu-mfma-vgpr-form, Makefile) nothing is copied.  Pinned
@@ -585,7 +544,7 @@ __global__ void __launch_bounds__(64 * W, 1)
     for (int qt = 0; qt < QT; ++qt)
 #pragma unroll
       for (int sb = 0; sb < 2; ++sb)
-        if (c < K1C_QAGPR) asm volatile("" : "+a"(qres[c][qt][sb]));
+        if (c < kK1cQAgpr) asm volatile("" : "+a"(qres[c][qt][sb]));
 #pragma unroll
   for (int c = 0; c < NQL; ++c)
 #pragma unroll
@@ -614,13 +573,12 @@ __global__ void __launch_bounds__(64 * W, 1)
   // the workgroup's chunks are contiguous in the plane: chunk gc = block run (cb + gc) * 8
   const int64_t cb = (r_begin >> 6) * KC;
   auto issue_piece = [&](int gc, int i) __attribute__((always_inline)) {
-    int gl = min(gc, total - 1);  // clamped: one control path past the end
-    if (dbg & 8192) gl &= 15;     // bit 13: ablation only (L2-resident source: LDS traffic without HBM)
+    const int gl = min(gc, total - 1);  // clamped: one control path past the end
     const int o = W * i + wave;
     __builtin_amdgcn_global_load_lds(Xb + (((cb + gl) * 8 + o) << 10) + plane_lane(lane) * 16,
                                      (__attribute__((address_space(3))) void *)(lds + LL::ring + (gc % RING) * 8192 +
                                                                                 o * 1024),
-                                     16, 0, K1C_AUX);
+                                     16, 0, kK1cAux);
   };
   auto issue = [&](int gc) __attribute__((always_inline)) {
 #pragma unroll
@@ -650,15 +608,11 @@ __global__ void __launch_bounds__(64 * W, 1)
     const int64_t row0 = r_begin + (int64_t)t * kRRows;
     const int64_t w0 = row0 >> 5;
     // lane (g, j) holds rows rt*16 + 4g + r: bit (16 rt + 4 g + r) of the 64-bit tile mask
-#ifdef K1C_NOMASK
-    const uint32_t b0 = 0xffffffffu, b1 = 0xffffffffu;  // timing ablation only: every row live
-#else
     const int wl = 2 * (t & 31);
     const uint32_t m0 = (uint32_t)__builtin_amdgcn_readlane((int)(lwin & awin), wl);
     const uint32_t m1 = (uint32_t)__builtin_amdgcn_readlane((int)(lwin & awin), wl + 1);
     const uint32_t b0 = w0 < n_words ? m0 : 0u;
     const uint32_t b1 = w0 + 1 < n_words ? m1 : 0u;
-#endif
     coarse_epilogue<QT, MINONLY>(acc, lane_live16(((uint64_t)b1 << 32) | b0, g), row0, sd, best, qcnt,
                                  out_keys + (((int64_t)qp * n_wg + wg) * kBQPass + qc0 + j) * kCBufCap);
 #pragma unroll
@@ -685,33 +639,18 @@ __global__ void __launch_bounds__(64 * W, 1)
     issue(RING - 1);
     f16x8 xf[4][2];
 #pragma unroll
-    for (int rt = 0; rt < (K1C_SCHED ? 2 : 4); ++rt) {  // interleaved schedule: chunk 0 reads its own 2-3
+    for (int rt = 0; rt < 2; ++rt) {  // chunk 0 reads its own row fragments 2-3 in its half 1
       xf[rt][0] = frag(0, rt, 0);
       xf[rt][1] = frag(0, rt, 1);
     }
     f16x8 ql[QT][2];  // query fragments of an LDS-resident chunk (c >= KR)
-    if (KR == 0) {
-#pragma unroll
-      for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-        for (int sb = 0; sb < 2; ++sb)
-          ql[qt][sb] = *reinterpret_cast<const f16x8 *>(lds + LL::qf + ((0 * W + wave) * NF + qt * 2 + sb) * 1024 +
-                                                        lane * 16);
-    }
     for (int t = 0; t < ntiles; ++t) {
       if ((t & 31) == 0) load_window(t);
 #pragma unroll
       for (int c = 0; c < KC; ++c) {
         const int gc = t * KC + c;
-#if defined(K1C_QV) && K1C_QV == 1  // timing ablations only: one resident chunk's fragments for all
-        auto qv = [&](int qt, int sb) -> f16x8 { return qres[0][qt][sb]; };
-#elif defined(K1C_QV) && K1C_QV == 2  // ... register fragments only (no LDS-resident chunks)
-        auto qv = [&](int qt, int sb) -> f16x8 { return qres[KR > 0 ? c % KR : 0][qt][sb]; };
-#else
         auto qv = [&](int qt, int sb) -> f16x8 { return c < KR ? qres[c < KR ? c : 0][qt][sb] : ql[qt][sb]; };
-#endif
         const int cn = (c + 1) % KC;  // next chunk's query fragments come from LDS when cn >= KR
-#if K1C_SCHED
         // Interleaved chunk schedule.  With one wave per SIMD nothing hides a non-MFMA instruction
         // but the MFMA issued just before it, so the chunk's LDS reads, counted wait, barrier and
         // DMA pieces are threaded one per MFMA through its 2 x MH MFMAs (sched_barrier-fenced):
@@ -723,108 +662,43 @@ __global__ void __launch_bounds__(64 * W, 1)
         //     query fragments follow the last MFMA of their q-tile group.
         // MFMA order within a half: q-tile group, k-half, row tile, q-tile (an accumulator recurs
         // every 2 QA MFMAs), so a q-tile group's fragments are free half-way through the half.
-        {
-          constexpr int QA = QT / 2, MH = 8 * QA;
-          auto mf = [&](int h, int m) __attribute__((always_inline)) {
-            const int qa = m % QA, rt = 2 * h + (m / QA) % 2, sb = (m / (2 * QA)) % 2, qt = (m / (4 * QA)) * QA + qa;
-            if (dbg & 4096) return;  // bit 12: ablation only (no MFMA: the memory side alone)
-            acc[rt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf[rt][sb], qv(qt, sb), acc[rt][qt], 0, 0, 0);
-          };
-          auto read_ql = [&](int grp) __attribute__((always_inline)) {
+        constexpr int QA = QT / 2, MH = 8 * QA;
+        auto mf = [&](int h, int m) __attribute__((always_inline)) {
+          const int qa = m % QA, rt = 2 * h + (m / QA) % 2, sb = (m / (2 * QA)) % 2, qt = (m / (4 * QA)) * QA + qa;
+          acc[rt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf[rt][sb], qv(qt, sb), acc[rt][qt], 0, 0, 0);
+        };
+        auto read_ql = [&](int grp) __attribute__((always_inline)) {
 #pragma unroll
-            for (int qa = 0; qa < QA; ++qa)
-#pragma unroll
-              for (int sb = 0; sb < 2; ++sb)
-                ql[grp * QA + qa][sb] = *reinterpret_cast<const f16x8 *>(
-                    lds + LL::qf + (((cn - KR) * W + wave) * NF + (grp * QA + qa) * 2 + sb) * 1024 + lane * 16);
-          };
-#pragma unroll
-          for (int m = 0; m < MH; ++m) {
-            mf(0, m);
-            __builtin_amdgcn_sched_barrier(0);
-            if (m < 4 && !(dbg & 2048)) xf[2 + m / 2][m % 2] = frag(gc, 2 + m / 2, m % 2);  // bit 11: ablation
-            const int w0 = MH - PCS - 2;
-            if (m == w0) {
-              asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(PCS * (RING - 2)) : "memory");
-              if (!(dbg & 512)) __builtin_amdgcn_s_barrier();  // bit 9: ablation only (races)
-            }
-            if (m > w0 && m <= w0 + PCS && !(dbg & 1024))  // bit 10: ablation only (stale data)
-              issue_piece(gc + RING, m - w0 - 1);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-#pragma unroll
-          for (int m = 0; m < MH; ++m) {
-            mf(1, m);
-            __builtin_amdgcn_sched_barrier(0);
-            if (m < 4 && !(dbg & 2048)) xf[m / 2][m % 2] = frag(gc + 1, m / 2, m % 2);
-            if (cn >= KR && m == MH / 2 - 1) read_ql(0);
-            if (cn >= KR && m == MH - 1) read_ql(1);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-#else
-        // half 1: row tiles 0, 1
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt) {
-#pragma unroll
-          for (int qt = 0; qt < QT; ++qt)
-            acc[rt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf[rt][0], qv(qt, 0), acc[rt][qt], 0, 0, 0);
-#pragma unroll
-          for (int qt = 0; qt < QT; ++qt)
-            acc[rt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf[rt][1], qv(qt, 1), acc[rt][qt], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // chunk gc+1 landed (this wave's pieces: the PCS (RING - 2) younger DMAs may stay in
-        // flight); own LDS reads of slot gc done; the barrier makes both true for every wave
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(PCS * (RING - 2)) : "memory");
-        if (!(dbg & 512)) __builtin_amdgcn_s_barrier();  // bit 9: ablation only (races)
-        if (!(dbg & 1024)) issue(gc + RING);             // bit 10: ablation only (stale data)
-#pragma unroll
-        for (int rt = 0; rt < ((dbg & 2048) ? 0 : 2); ++rt) {  // bit 11: ablation only (stale fragments)
-          xf[rt][0] = frag(gc + 1, rt, 0);
-          xf[rt][1] = frag(gc + 1, rt, 1);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // half 2: row tiles 2, 3
-#pragma unroll
-        for (int rt = 2; rt < 4; ++rt) {
-#pragma unroll
-          for (int qt = 0; qt < QT; ++qt)
-            acc[rt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf[rt][0], qv(qt, 0), acc[rt][qt], 0, 0, 0);
-#pragma unroll
-          for (int qt = 0; qt < QT; ++qt)
-            acc[rt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf[rt][1], qv(qt, 1), acc[rt][qt], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int rt = 2; rt < ((dbg & 2048) ? 2 : 4); ++rt) {  // bit 11: ablation only (stale fragments)
-          xf[rt][0] = frag(gc + 1, rt, 0);
-          xf[rt][1] = frag(gc + 1, rt, 1);
-        }
-        if (cn >= KR) {
-#pragma unroll
-          for (int qt = 0; qt < QT; ++qt)
+          for (int qa = 0; qa < QA; ++qa)
 #pragma unroll
             for (int sb = 0; sb < 2; ++sb)
-              ql[qt][sb] = *reinterpret_cast<const f16x8 *>(
-                  lds + LL::qf + (((cn - KR) * W + wave) * NF + qt * 2 + sb) * 1024 + lane * 16);
+              ql[grp * QA + qa][sb] = *reinterpret_cast<const f16x8 *>(
+                  lds + LL::qf + (((cn - KR) * W + wave) * NF + (grp * QA + qa) * 2 + sb) * 1024 + lane * 16);
+        };
+#pragma unroll
+        for (int m = 0; m < MH; ++m) {
+          mf(0, m);
+          __builtin_amdgcn_sched_barrier(0);
+          if (m < 4) xf[2 + m / 2][m % 2] = frag(gc, 2 + m / 2, m % 2);
+          const int w0 = MH - PCS - 2;
+          if (m == w0) {
+            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(PCS * (RING - 2)) : "memory");
+            __builtin_amdgcn_s_barrier();
+          }
+          if (m > w0 && m <= w0 + PCS) issue_piece(gc + RING, m - w0 - 1);
+          __builtin_amdgcn_sched_barrier(0);
         }
-        __builtin_amdgcn_sched_barrier(0);
-#endif
-      }
-#ifdef K1C_EPI0  // timing ablation only: keep the MFMAs alive with a trivial epilogue
-      {
-        float z = 0.f;
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-          for (int qt = 0; qt < QT; ++qt) z += acc[rt][qt][0];
-        best[0] = fminf(best[0], z);
-        qcnt[0] += z == 12345.f ? 1u : 0u;  // observable: out_cnt / out_min
+        for (int m = 0; m < MH; ++m) {
+          mf(1, m);
+          __builtin_amdgcn_sched_barrier(0);
+          if (m < 4) xf[m / 2][m % 2] = frag(gc + 1, m / 2, m % 2);
+          if (cn >= KR && m == MH / 2 - 1) read_ql(0);
+          if (cn >= KR && m == MH - 1) read_ql(1);
+          __builtin_amdgcn_sched_barrier(0);
+        }
       }
-#else
-      if (!(dbg & 128)) epilogue(t);
-#endif
+      epilogue(t);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // clamped tail DMAs land before the LDS is released
   }
@@ -902,7 +776,7 @@ __global__ void __launch_bounds__(256, 1)
       const int gl = min(gc, total - 1);  // clamped: one control path past the end
       const f16x8 *p = Xv + (tile0 * KC + gl) * 512 + plane_lane(lane);  // the wave's chunks are contiguous
 #pragma unroll
-      for (int i = 0; i < 8; ++i) b[i] = K1S_NT ? __builtin_nontemporal_load(p + i * 64) : p[i * 64];
+      for (int i = 0; i < 8; ++i) b[i] = kK1sNt ? __builtin_nontemporal_load(p + i * 64) : p[i * 64];
     };
 #pragma unroll
     for (int p = 0; p < R - 1; ++p) load(xb[p], p);
@@ -969,10 +843,9 @@ __device__ inline uint32_t block_select_u32(const uint32_t *vals, int n, int kk,
   return block_select_fn([&](int i) { return vals[i]; }, n, kk, hist);
 }
 
-// seed[q] = the k-th smallest per-group minimum + add_err x E: K1c / K1s add 2E (their minima are
-// coarse f16 distances and their scans test the coarse distance against the seed), K1q seeded from
-// the same f16 sample adds E (its scan tests a lower bound of the true distance), K1q seeded from
-// its own int8 sample adds nothing (those minima already carry their rows' bounds)
+// seed[q] = the k-th smallest per-group minimum + add_err x E.  The minima are coarse f16 distances
+// of the sample pass (K1c / K1s MINONLY).  add_err = 2 for K1c / K1s, whose scans test the coarse
+// distance against the seed; 1 for K1q / K1q-s, whose scans test a lower bound of the true distance.
 __global__ void __launch_bounds__(256) dense_seed_kernel(const float *__restrict__ mins, int n_wg, int qs, int k,
                                                          int nq, const float *__restrict__ qnorm,
                                                          const float *__restrict__ row_norms, int dim,
@@ -989,8 +862,7 @@ __global__ void __launch_bounds__(256) dense_seed_kernel(const float *__restrict
   // the O(n^2) rank count it replaces took ~0.1 ms per single-query search)
   const float kth = n >= k ? f32_unorder(block_select_u32(v, n, k - 1, hist)) : __builtin_inff();
   if (threadIdx.x == 0)
-    seed[qi] = kth < __builtin_inff() ? (add_err ? kth + (float)add_err * coarse_err(qnorm, qi, row_norms, dim) : kth)
-                                      : __builtin_inff();
+    seed[qi] = kth < __builtin_inff() ? kth + (float)add_err * coarse_err(qnorm, qi, row_norms, dim) : __builtin_inff();
 }
 
 // K1c certification + exact re-rank, one 256-thread workgroup per query.
@@ -1435,7 +1307,7 @@ struct DenseWs {
   size_t total;
 };
 
-DenseWs dense_ws_layout(const cm_dense *h, const DenseCfg &c, int nq, int k, void *base) {
+DenseWs dense_ws_layout(const cm_dense *h, const DenseCfg &c, int k, void *base) {
   DenseWs w{};
   char *p = reinterpret_cast<char *>(base);
   size_t off = 0;
@@ -1447,7 +1319,6 @@ DenseWs dense_ws_layout(const cm_dense *h, const DenseCfg &c, int nq, int k, voi
   w.cand = reinterpret_cast<uint64_t *>(p + off);
   off += round_up((int64_t)c.n_qgroups * c.n_cblocks * c.QB * k * 8, 256);
   w.total = off;
-  (void)nq;
   return w;
 }
 
@@ -1673,20 +1544,6 @@ int dense_grow(cm_dense *h, int64_t need_rows) {
   return dense_realloc(h, cap, staged);
 }
 
-// Timing ablations are compiled only into -DCM_ABLATION builds (tools/build_variant.sh); the
-// product library ignores CM_DENSE_DEBUG, so no bench line can come from a disabled kernel.
-#ifdef CM_ABLATION
-int dense_debug_flags() {
-  static const int f = [] {
-    const char *e = getenv("CM_DENSE_DEBUG");
-    return e ? atoi(e) : 0;
-  }();
-  return f;
-}
-#else
-int dense_debug_flags() { return 0; }
-#endif
-
 // Scan kernel for (nq, k), the "search kind":
 //   CM_DENSE_Q8S   (K1q-s) dim-768, nq <= kSQ: per-wave HBM streams of the int8 plane + re-rank;
 //   CM_DENSE_Q8    (K1q)   dim-768 batches nq > kSQ: int8 plane, 256-query resident passes + re-rank;
@@ -1731,28 +1588,6 @@ int dense_kind(const cm_dense *h, int nq, int k) {
 // Coarse-scan geometry.  K1c: a pass of kBQPass queries per workgroup, one workgroup per CU and
 // pass; K1s: one pass of kSQ queries, n_wg = "virtual groups" = waves (4 per CU).  The sample
 // pre-pass runs the same kernel over a prefix of 1/64 of the rows (1/16 below 1M rows).
-// K1c form: whole passes (QPASS 256, LDS ring + LDS-resident query chunks; default) or paired
-// half passes (QPASS 128, 20-slot ring, CM_K1C_PAIRED=1).  Measured at 10M x 768, B = 256:
-// 4.5 vs 6.0 ms -- the ring depth is not what limits the scan (4 slots run as fast as 8).
-bool k1c_paired() {
-  static const bool p = [] {
-    const char *e = getenv("CM_K1C_PAIRED");
-    return e && e[0] == '1';
-  }();
-  return p;
-}
-
-// K1q's seed: by default the K1c MINONLY scan over a 1/16 row sample of the f16 plane (its bound E is
-// ~30x tighter than the int8 plane's, so the seed lands near the sample's k-th distance and the scan
-// appends ~3x fewer candidates: 4-14k -> ~3k per query at 10M, profiles/r04b_k1q_abl.txt);
-// CM_K1Q_SEED=q8 keeps the int8 MINONLY pass over a 1/8 sample (A/B).
-bool k1q_seed_q8() {
-  static const bool v = [] {
-    const char *e = getenv("CM_K1Q_SEED");
-    return e && std::string(e) == "q8";
-  }();
-  return v;
-}
 int64_t k1qs_sample_frac() {
   // K1q-s's f16 seed sample: 1/32 of the rows (10M x 768, k = 24: B = 1 1.48 / B = 16 1.61 ms per search
   // vs 1.54 / 1.64 at 1/16 and 1.47 / 1.76 at 1/64 -- a thinner sample's looser seed costs the 16-query
@@ -1764,25 +1599,23 @@ int64_t k1qs_sample_frac() {
   }();
   return v;
 }
+// K1q's seed: the K1c MINONLY scan over a 1/16 row sample of the f16 plane (its bound E is ~30x
+// tighter than the int8 plane's, so the seed lands near the sample's k-th distance and the scan
+// appends ~3x fewer candidates than an int8 sample pass did: 4-14k -> ~3k per query at 10M,
+// profiles/r04b_k1q_abl.txt)
 int64_t k1q_sample_frac() {
   static const int64_t v = [] {   // $CM_K1Q_SAMPLE = 1/fraction of the rows in the seed sample (A/B knob)
     const char *e = getenv("CM_K1Q_SAMPLE");
     const int64_t f = e ? atoll(e) : 0;
-    return f >= 2 && f <= 256 ? f : (k1q_seed_q8() ? (int64_t)kQSampleFrac : 16);
+    return f >= 2 && f <= 256 ? f : (int64_t)16;
   }();
   return v;
 }
 
 struct CoarseCfg {
-  bool stream, paired, q8, q8s;
+  bool stream, q8, q8s;
   int qs, n_pass, n_wg, n_wg_sample;
   int64_t rows_per_wg, rows_end, rows_per_wg_sample, rows_end_sample;
-  // blocks of a K1c launch over n_wg ranges: the paired form maps blocks b, b + 8 to one (pass,
-  // range) and pads the grid to whole groups of 16
-  unsigned grid(int ranges) const {
-    const int64_t m = (int64_t)n_pass * ranges;
-    return (unsigned)(paired ? round_up(2 * m, 16) : m);
-  }
 };
 CoarseCfg coarse_config(const cm_dense *h, int nq, int kind) {
   CoarseCfg c{};
@@ -1790,7 +1623,6 @@ CoarseCfg coarse_config(const cm_dense *h, int nq, int kind) {
   c.stream = stream;
   c.q8s = kind == CM_DENSE_Q8S;
   c.q8 = kind == CM_DENSE_Q8 || c.q8s;                                    // int8 buffers + re-rank
-  c.paired = !stream && !c.q8 && k1c_paired();
   c.qs = stream ? kSQ : kBQPass;
   c.n_pass = stream ? 1 : (int)ceil_div(nq, kBQPass);
   c.rows_end = round_up(std::max<int64_t>(h->size, 1), kStepRows);
@@ -1798,9 +1630,8 @@ CoarseCfg coarse_config(const cm_dense *h, int nq, int kind) {
   // (more workgroups than CUs) -- fewer, longer groups would overflow the 128-slot (group, query)
   // buffers and send the whole batch to the exact pass
   constexpr int64_t kMinGroups = 64;
-  int64_t groups = stream ? (int64_t)num_cus(h->dev) * 4
+  const int64_t groups = stream ? (int64_t)num_cus(h->dev) * 4
                           : std::max<int64_t>(kMinGroups, std::max(1, num_cus(h->dev) / c.n_pass));
-  if (c.paired) groups = std::max<int64_t>(1, groups / 2);
   auto split = [&](int64_t rows_end, int64_t g, int64_t &per, int &n) {
     const int64_t tiles = rows_end / kRRows;
     per = ceil_div(tiles, std::min<int64_t>(g, tiles)) * kRRows;
@@ -1868,7 +1699,7 @@ CoarseWs coarse_ws_layout(const cm_dense *h, const CoarseCfg &c, int nq, int k, 
     w.wide_keys = reinterpret_cast<uint64_t *>(take((int64_t)kWideSlots * kWideCap * 8));
   }
   const DenseCfg kc = dense_config(h, nq, k, true);
-  w.k1 = dense_ws_layout(h, kc, nq, k, p ? p + off : nullptr);
+  w.k1 = dense_ws_layout(h, kc, k, p ? p + off : nullptr);
   off += w.k1.total;
   w.total = off;
   return w;
@@ -1879,19 +1710,13 @@ int set_coarse_attrs() {
   static hipError_t err = hipSuccess;
   std::call_once(once, [] {
     const std::pair<const void *, int> fs[] = {
-        {reinterpret_cast<const void *>(&dense_coarse_scan_kernel<12, kK1cNql, false, kK1cWaves>), K1rLds<kK1cNql>::total},
-        {reinterpret_cast<const void *>(&dense_coarse_scan_kernel<12, kK1cNql, true, kK1cWaves>), K1rLds<kK1cNql>::total},
-        {reinterpret_cast<const void *>(&dense_coarse_scan_kernel<6, 0, false, kK1cWaves>), K1rLds<0>::total},
-        {reinterpret_cast<const void *>(&dense_coarse_scan_kernel<6, 0, true, kK1cWaves>), K1rLds<0>::total},
-        {reinterpret_cast<const void *>(&dense_coarse_scan_kernel<12, 0, false, 4, 20, 128>), K1rLds<0, 20>::total},
-        {reinterpret_cast<const void *>(&dense_coarse_scan_kernel<12, 0, true, 4, 20, 128>), K1rLds<0, 20>::total},
-        {reinterpret_cast<const void *>(&dense_coarse_scan_kernel<6, 0, false, 4, 20, 128>), K1rLds<0, 20>::total},
-        {reinterpret_cast<const void *>(&dense_coarse_scan_kernel<6, 0, true, 4, 20, 128>), K1rLds<0, 20>::total},
+        {reinterpret_cast<const void *>(&dense_coarse_scan_kernel<12, kK1cNql, false>), K1rLds<kK1cNql>::total},
+        {reinterpret_cast<const void *>(&dense_coarse_scan_kernel<12, kK1cNql, true>), K1rLds<kK1cNql>::total},
+        {reinterpret_cast<const void *>(&dense_coarse_scan_kernel<6, 0, false>), K1rLds<0>::total},
+        {reinterpret_cast<const void *>(&dense_coarse_scan_kernel<6, 0, true>), K1rLds<0>::total},
         {reinterpret_cast<const void *>(&dense_rerank_kernel), kGatherCap * 12},
-        {reinterpret_cast<const void *>(&dense_q8_scan_kernel<false>), kQLds},
-        {reinterpret_cast<const void *>(&dense_q8_scan_kernel<true>), kQLds},
-        {reinterpret_cast<const void *>(&dense_q8_scan_kernel<true, K1Q_LDS_SHARED>), kQLdsShared},
-        {reinterpret_cast<const void *>(&dense_q8_scan_kernel<false, K1Q_LDS_SHARED>), kQLdsShared},
+        {reinterpret_cast<const void *>(&dense_q8_scan_kernel<>), kQLds},
+        {reinterpret_cast<const void *>(&dense_q8_scan_kernel<K1Q_LDS_SHARED>), kQLdsShared},
         {reinterpret_cast<const void *>(&dense_rerank_q8_kernel), kQRerankLds}};
     for (const auto &f : fs) {
       const hipError_t e = hipFuncSetAttribute(f.first, hipFuncAttributeMaxDynamicSharedMemorySize, f.second);
@@ -1902,6 +1727,7 @@ int set_coarse_attrs() {
   return CM_OK;
 }
 
+// The scan kernels' instances, picked by the plane's ld and the batch.
 using StreamFn = void (*)(const _Float16 *, const uint32_t *, const uint32_t *, int64_t, const _Float16 *, int,
                           const float *, int64_t, int64_t, int, int, uint64_t *, uint32_t *, float *);
 StreamFn stream_kernel(int ld, int nq, bool minonly) {
@@ -1912,8 +1738,27 @@ StreamFn stream_kernel(int ld, int nq, bool minonly) {
   return two ? (minonly ? &dense_stream_scan_kernel<6, 2, true> : &dense_stream_scan_kernel<6, 2, false>)
              : (minonly ? &dense_stream_scan_kernel<6, 1, true> : &dense_stream_scan_kernel<6, 1, false>);
 }
+using CoarseFn = void (*)(const _Float16 *, const uint32_t *, const uint32_t *, int64_t, const _Float16 *, int,
+                          const float *, int64_t, int64_t, int, uint64_t *, uint32_t *, float *);
+CoarseFn coarse_kernel(int ld, bool minonly, size_t &lds) {   // K1c, and its dynamic LDS
+  if (ld == 768) {
+    lds = K1rLds<kK1cNql>::total;
+    return minonly ? &dense_coarse_scan_kernel<12, kK1cNql, true> : &dense_coarse_scan_kernel<12, kK1cNql, false>;
+  }
+  lds = K1rLds<0>::total;
+  return minonly ? &dense_coarse_scan_kernel<6, 0, true> : &dense_coarse_scan_kernel<6, 0, false>;
+}
+using Q8Fn = void (*)(const int8_t *, const float2 *, const uint32_t *, const uint32_t *, int64_t, const int8_t *,
+                      const float4 *, int, const float *, int64_t, int64_t, int, uint64_t *, float *, uint32_t *);
+Q8Fn q8_kernel(bool full, size_t &lds) {   // K1q: the full or the shared LDS footprint
+  lds = full ? kQLds : kQLdsShared;
+  return full ? &dense_q8_scan_kernel<> : &dense_q8_scan_kernel<K1Q_LDS_SHARED>;
+}
+Q8Fn q8_stream_kernel(int nq) {   // K1q-s: one or two q-tiles
+  return nq > 16 ? &dense_q8_stream_kernel<2, K1QS_RING> : &dense_q8_stream_kernel<1, K1QS_RING>;
+}
 
-// K1c / K1s: sample pre-pass -> seed -> coarse scan -> certificate + exact re-rank; the queries
+// The coarse kinds: prep -> sample pre-pass -> seed -> scan -> certificate + re-rank; the queries
 // whose certificate fails (fb_mask) are re-searched by the exact fp32 K1 and merged (every
 // workgroup of those launches exits at once when there are none: graph-capturable, no host sync).
 int launch_exact_fallback(cm_dense *h, const float *q_dev, int nq, int k, int kind, const uint32_t *allow,
@@ -1923,139 +1768,81 @@ int launch_coarse(cm_dense *h, const float *q_dev, int nq, int k, int kind, cons
                   bool run_exact = true) {
   int rc;
   if ((rc = set_coarse_attrs())) return rc;
-  const bool stream = kind == CM_DENSE_STREAM;
   const CoarseCfg c = coarse_config(h, nq, kind);
   const CoarseWs w = coarse_ws_layout(h, c, nq, k, ws);
   if ((int64_t)w.total > ws_bytes || !ws) CM_FAIL(CM_EINVAL, "dense workspace too small");
   const int64_t n_words = ceil_div(h->size, 32);
+  size_t lds = 0;
+  // 1. prep: normalised f16 queries; the int8 kinds' int8 queries
   hipLaunchKernelGGL(dense_prep_planes, dim3(c.n_pass * c.qs), dim3(256), 0, st, q_dev, nq, h->dim, h->ld, w.qh,
                      w.qnorm);
   CM_HIP(hipGetLastError());
   CM_HIP(hipMemsetAsync(w.fb_count, 0, 4, st));
-  if (c.q8) CM_HIP(hipMemsetAsync(w.wide_ctr, 0, 8, st));
   if (c.q8) {
-    // K1q: int8 queries -> seed from a row sample -> scan -> certified re-rank (int8 band -> f16 band
-    // -> fp64)
+    CM_HIP(hipMemsetAsync(w.wide_ctr, 0, 8, st));
     hipLaunchKernelGGL(dense_prep_q8, dim3(c.n_pass * c.qs), dim3(256), 0, st, q_dev, nq, h->dim, h->ld, w.qq, w.qsc,
                        reinterpret_cast<const uint32_t *>(h->rnorm));
     CM_HIP(hipGetLastError());
-    if (c.q8s) {   // K1q-s: K1s's MINONLY stream over the f16 plane's sample, then the int8 stream
-      hipLaunchKernelGGL(stream_kernel(h->ld, nq, true), dim3((unsigned)ceil_div(c.n_wg_sample, 4)), dim3(256), 0, st,
-                         h->Xh, h->live, allow, n_words, w.qh, nq, (const float *)nullptr, c.rows_per_wg_sample,
-                         c.rows_end_sample, c.n_wg_sample, c.qs, (uint64_t *)nullptr, (uint32_t *)nullptr, w.mins);
-      CM_HIP(hipGetLastError());
-      hipLaunchKernelGGL(dense_seed_kernel, dim3(nq), dim3(256), 0, st, w.mins, c.n_wg_sample, c.qs, k, nq, w.qnorm,
-                         h->rnorm, h->dim, w.seed, 1);
-      CM_HIP(hipGetLastError());
-      h->timer.begin(st);
-      if (nq > 16)
-        hipLaunchKernelGGL((dense_q8_stream_kernel<2, K1QS_RING>), dim3((unsigned)ceil_div(c.n_wg, 4)), dim3(256), 0, st,
-                           h->Xq, h->rmeta, h->live, allow, n_words, w.qq, w.qsc, nq, (const float *)w.seed,
-                           c.rows_per_wg, c.rows_end, c.n_wg, w.keys, w.ups, w.cnt);
-      else
-        hipLaunchKernelGGL((dense_q8_stream_kernel<1, K1QS_RING>), dim3((unsigned)ceil_div(c.n_wg, 4)), dim3(256), 0, st,
-                           h->Xq, h->rmeta, h->live, allow, n_words, w.qq, w.qsc, nq, (const float *)w.seed,
-                           c.rows_per_wg, c.rows_end, c.n_wg, w.keys, w.ups, w.cnt);
-      h->timer.end(st);
-      CM_HIP(hipGetLastError());
-    } else {
-    if (k1q_seed_q8()) {   // (deferred search: the shared LDS footprint, beside the BM25 blocks)
-      if (run_exact || !env_knob("CM_K1Q_SHARED_LDS", true))
-        hipLaunchKernelGGL(dense_q8_scan_kernel<true>, dim3(c.n_pass * c.n_wg_sample), dim3(256), kQLds, st, h->Xq,
-                           h->rmeta, h->live, allow, n_words, w.qq, w.qsc, nq, (const float *)nullptr,
-                           c.rows_per_wg_sample, c.rows_end_sample, c.n_wg_sample, (uint64_t *)nullptr,
-                           (float *)nullptr, (uint32_t *)nullptr, w.mins);
-      else
-        hipLaunchKernelGGL((dense_q8_scan_kernel<true, K1Q_LDS_SHARED>), dim3(c.n_pass * c.n_wg_sample), dim3(256),
-                           kQLdsShared, st, h->Xq, h->rmeta, h->live, allow, n_words, w.qq, w.qsc, nq,
-                           (const float *)nullptr, c.rows_per_wg_sample, c.rows_end_sample, c.n_wg_sample,
-                           (uint64_t *)nullptr, (float *)nullptr, (uint32_t *)nullptr, w.mins);
-    } else {   // K1c MINONLY over the f16 plane's sample (dim 768: the resident-query instance)
-      hipLaunchKernelGGL((dense_coarse_scan_kernel<12, kK1cNql, true, kK1cWaves>), dim3(c.grid(c.n_wg_sample)),
-                         dim3(64 * kK1cWaves), K1rLds<kK1cNql>::total, st, h->Xh, h->live, allow, n_words, w.qh, nq,
-                         (const float *)nullptr, c.rows_per_wg_sample, c.rows_end_sample, c.n_wg_sample,
-                         (uint64_t *)nullptr, (uint32_t *)nullptr, w.mins, 0);
-    }
-    CM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(dense_seed_kernel, dim3(nq), dim3(256), 0, st, w.mins, c.n_wg_sample, c.qs, k, nq, w.qnorm,
-                       h->rnorm, h->dim, w.seed, k1q_seed_q8() ? 0 : 1);
-    CM_HIP(hipGetLastError());
-    if (h->seed_event) CM_HIP(hipEventRecord(h->seed_event, st));
-    h->timer.begin(st);
-    // deferred search (!run_exact): the caller runs other work beside it -> the shared LDS footprint
-    // (CM_K1Q_SHARED_LDS=0: the full one, A/B)
-    if (run_exact || !env_knob("CM_K1Q_SHARED_LDS", true))
-      hipLaunchKernelGGL(dense_q8_scan_kernel<false>, dim3(c.n_pass * c.n_wg), dim3(256), kQLds, st, h->Xq,
-                         h->rmeta, h->live, allow, n_words, w.qq, w.qsc, nq, (const float *)w.seed, c.rows_per_wg,
-                         c.rows_end, c.n_wg, w.keys, w.ups, w.cnt, (float *)nullptr);
-    else
-      hipLaunchKernelGGL((dense_q8_scan_kernel<false, K1Q_LDS_SHARED>), dim3(c.n_pass * c.n_wg), dim3(256), kQLdsShared,
-                         st, h->Xq, h->rmeta, h->live, allow, n_words, w.qq, w.qsc, nq, (const float *)w.seed,
-                         c.rows_per_wg, c.rows_end, c.n_wg, w.keys, w.ups, w.cnt, (float *)nullptr);
-    h->timer.end(st);
-    CM_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(dense_rerank_q8_kernel, dim3(nq), dim3(kQRT), kQRerankLds, st, w.keys, w.ups, w.cnt, c.n_wg, c.qs, k,
-                       nq, h->C, h->ld, h->dim, q_dev, w.qsc, xh_full(h) ? h->Xh : nullptr, w.qh, w.qnorm, h->rnorm,
-                       dist_dev, row_dev,
-                       w.fb_mask, w.fb_count, w.fb_bound);
-    CM_HIP(hipGetLastError());
-    // band overflow with complete candidate buffers: the wide re-rank (gated; ~5 us when none failed;
-    // CM_K1Q_WIDE=0: the exact scan takes every failing query, A/B)
-    if (env_knob("CM_K1Q_WIDE", true))
-      hipLaunchKernelGGL(dense_rerank_wide_kernel, dim3(nq), dim3(kWideThreads), 0, st, w.keys, w.cnt, c.n_wg, c.qs, k,
-                         nq, h->C, h->ld, h->dim, q_dev, w.qsc, xh_full(h) ? h->Xh : nullptr, w.qh, w.qnorm, h->rnorm,
-                         h->Xq, h->rmeta, w.qq, h->live, allow,
-                         n_words, c.rows_per_wg, c.rows_end, dist_dev, row_dev, w.fb_mask, w.fb_count, w.fb_bound, w.wide_ctr,
-                         w.wide_rows, w.wide_keys);
-    CM_HIP(hipGetLastError());
-  } else {
-  const bool d768 = h->ld == 768;
-  const size_t slds = c.paired ? K1rLds<0, 20>::total : d768 ? K1rLds<kK1cNql>::total : K1rLds<0>::total;
-  const int k1c_threads = c.paired ? 256 : 64 * kK1cWaves;
-  auto k1c = [&](bool minonly) {
-    if (c.paired) {
-      if (d768)
-        return minonly ? &dense_coarse_scan_kernel<12, 0, true, 4, 20, 128>
-                       : &dense_coarse_scan_kernel<12, 0, false, 4, 20, 128>;
-      return minonly ? &dense_coarse_scan_kernel<6, 0, true, 4, 20, 128>
-                     : &dense_coarse_scan_kernel<6, 0, false, 4, 20, 128>;
-    }
-    if (d768) return minonly ? &dense_coarse_scan_kernel<12, kK1cNql, true, kK1cWaves> : &dense_coarse_scan_kernel<12, kK1cNql, false, kK1cWaves>;
-    return minonly ? &dense_coarse_scan_kernel<6, 0, true, kK1cWaves> : &dense_coarse_scan_kernel<6, 0, false, kK1cWaves>;
-  };
-  // 1. sample pre-pass (per-group minima) -> seed
-  if (stream) {
+  }
+  // 2. sample pre-pass over the f16 plane's sample prefix (per-group minima): K1s or K1c, MINONLY
+  if (c.stream) {
     hipLaunchKernelGGL(stream_kernel(h->ld, nq, true), dim3((unsigned)ceil_div(c.n_wg_sample, 4)), dim3(256), 0, st,
                        h->Xh, h->live, allow, n_words, w.qh, nq, (const float *)nullptr, c.rows_per_wg_sample,
                        c.rows_end_sample, c.n_wg_sample, c.qs, (uint64_t *)nullptr, (uint32_t *)nullptr, w.mins);
   } else {
-    hipLaunchKernelGGL(k1c(true), dim3(c.grid(c.n_wg_sample)), dim3(k1c_threads), slds, st, h->Xh, h->live,
+    const CoarseFn fn = coarse_kernel(h->ld, true, lds);
+    hipLaunchKernelGGL(fn, dim3((unsigned)((int64_t)c.n_pass * c.n_wg_sample)), dim3(256), lds, st, h->Xh, h->live,
                        allow, n_words, w.qh, nq, (const float *)nullptr, c.rows_per_wg_sample, c.rows_end_sample,
-                       c.n_wg_sample, (uint64_t *)nullptr, (uint32_t *)nullptr, w.mins, 0);
+                       c.n_wg_sample, (uint64_t *)nullptr, (uint32_t *)nullptr, w.mins);
   }
   CM_HIP(hipGetLastError());
+  // 3. seed
   hipLaunchKernelGGL(dense_seed_kernel, dim3(nq), dim3(256), 0, st, w.mins, c.n_wg_sample, c.qs, k, nq, w.qnorm,
-                     h->rnorm, h->dim, w.seed, 2);
+                     h->rnorm, h->dim, w.seed, c.q8 ? 1 : 2);
   CM_HIP(hipGetLastError());
-  // 2. coarse scan: rows under the seed -> candidate buffers
+  if (kind == CM_DENSE_Q8 && h->seed_event) CM_HIP(hipEventRecord(h->seed_event, st));
+  // 4. scan: rows under the seed -> candidate buffers
   h->timer.begin(st);
-  if (stream) {
+  if (c.q8s) {
+    hipLaunchKernelGGL(q8_stream_kernel(nq), dim3((unsigned)ceil_div(c.n_wg, 4)), dim3(256), 0, st, h->Xq, h->rmeta,
+                       h->live, allow, n_words, w.qq, w.qsc, nq, (const float *)w.seed, c.rows_per_wg, c.rows_end,
+                       c.n_wg, w.keys, w.ups, w.cnt);
+  } else if (c.q8) {
+    // deferred search (!run_exact): the caller runs other work beside it -> the shared LDS footprint
+    // (CM_K1Q_SHARED_LDS=0: the full one, A/B)
+    const Q8Fn fn = q8_kernel(run_exact || !env_knob("CM_K1Q_SHARED_LDS", true), lds);
+    hipLaunchKernelGGL(fn, dim3(c.n_pass * c.n_wg), dim3(256), lds, st, h->Xq, h->rmeta, h->live, allow, n_words,
+                       w.qq, w.qsc, nq, (const float *)w.seed, c.rows_per_wg, c.rows_end, c.n_wg, w.keys, w.ups, w.cnt);
+  } else if (c.stream) {
     hipLaunchKernelGGL(stream_kernel(h->ld, nq, false), dim3((unsigned)ceil_div(c.n_wg, 4)), dim3(256), 0, st, h->Xh,
                        h->live, allow, n_words, w.qh, nq, (const float *)w.seed, c.rows_per_wg, c.rows_end, c.n_wg,
                        c.qs, w.keys, w.cnt, (float *)nullptr);
   } else {
-    hipLaunchKernelGGL(k1c(false), dim3(c.grid(c.n_wg)), dim3(k1c_threads), slds, st, h->Xh, h->live, allow,
+    const CoarseFn fn = coarse_kernel(h->ld, false, lds);
+    hipLaunchKernelGGL(fn, dim3((unsigned)((int64_t)c.n_pass * c.n_wg)), dim3(256), lds, st, h->Xh, h->live, allow,
                        n_words, w.qh, nq, (const float *)w.seed, c.rows_per_wg, c.rows_end, c.n_wg, w.keys, w.cnt,
-                       (float *)nullptr, dense_debug_flags());
+                       (float *)nullptr);
   }
   h->timer.end(st);
   CM_HIP(hipGetLastError());
-  // 3. certificate + exact re-rank (failures -> fb_mask)
-  hipLaunchKernelGGL(dense_rerank_kernel, dim3(nq), dim3(256), kGatherCap * 12, st, w.keys, w.cnt, c.n_wg, c.qs, k,
-                     nq, h->C, h->ld, h->dim, q_dev, w.qnorm, h->rnorm, dist_dev, row_dev, w.fb_mask, w.fb_count);
-  CM_HIP(hipGetLastError());
+  // 5. certificate + exact re-rank (failures -> fb_mask)
+  if (c.q8) {
+    hipLaunchKernelGGL(dense_rerank_q8_kernel, dim3(nq), dim3(kQRT), kQRerankLds, st, w.keys, w.ups, w.cnt, c.n_wg,
+                       c.qs, k, nq, h->C, h->ld, h->dim, q_dev, w.qsc, xh_full(h) ? h->Xh : nullptr, w.qh, w.qnorm,
+                       h->rnorm, dist_dev, row_dev, w.fb_mask, w.fb_count, w.fb_bound);
+    CM_HIP(hipGetLastError());
+    // band overflow with complete candidate buffers: the wide re-rank (gated; ~5 us when none failed;
+    // CM_K1Q_WIDE=0: the exact scan takes every failing query, A/B)
+    if (env_knob("CM_K1Q_WIDE", true))
+      hipLaunchKernelGGL(dense_rerank_wide_kernel, dim3(nq), dim3(kWideThreads), 0, st, w.keys, w.cnt, c.n_wg, c.qs,
+                         k, nq, h->C, h->ld, h->dim, q_dev, w.qsc, xh_full(h) ? h->Xh : nullptr, w.qh, w.qnorm,
+                         h->rnorm, h->Xq, h->rmeta, w.qq, h->live, allow, n_words, c.rows_per_wg, c.rows_end, dist_dev,
+                         row_dev, w.fb_mask, w.fb_count, w.fb_bound, w.wide_ctr, w.wide_rows, w.wide_keys);
+  } else {
+    hipLaunchKernelGGL(dense_rerank_kernel, dim3(nq), dim3(256), kGatherCap * 12, st, w.keys, w.cnt, c.n_wg, c.qs, k,
+                       nq, h->C, h->ld, h->dim, q_dev, w.qnorm, h->rnorm, dist_dev, row_dev, w.fb_mask, w.fb_count);
   }
+  CM_HIP(hipGetLastError());
   return run_exact ? launch_exact_fallback(h, q_dev, nq, k, kind, allow, dist_dev, row_dev, ws, ws_bytes, st) : CM_OK;
 }
 
@@ -2341,7 +2128,7 @@ int64_t cm_dense_search_workspace(cm_dense *h, int32_t nq, int32_t k) {
   if (kind != CM_DENSE_F32)
     return (int64_t)coarse_ws_layout(h, coarse_config(h, nq, kind), nq, k, nullptr).total;
   DenseCfg c = dense_config(h, nq, k);
-  return (int64_t)dense_ws_layout(h, c, nq, k, nullptr).total;
+  return (int64_t)dense_ws_layout(h, c, k, nullptr).total;
 }
 
 int cm_dense_set_path(cm_dense *h, int32_t kind) {
@@ -2418,7 +2205,7 @@ int cm_dense_search_dev(cm_dense *h, const float *q_dev, int32_t nq, int32_t k, 
     return launch_coarse(h, q_dev, nq, k, kind, allow_dev, dist_dev, row_dev, workspace_dev, workspace_bytes, st);
   DenseCfg c = dense_config(h, nq, k);
   if (c.lds > 163840) CM_FAIL(CM_EUNSUPPORTED, "dim/k too large for the LDS-resident query tile");
-  DenseWs w = dense_ws_layout(h, c, nq, k, workspace_dev);
+  DenseWs w = dense_ws_layout(h, c, k, workspace_dev);
   if ((int64_t)w.total > workspace_bytes || !workspace_dev) CM_FAIL(CM_EINVAL, "dense workspace too small");
   const int nq_pad = c.n_qgroups * c.QB;
   hipLaunchKernelGGL(dense_prep_queries, dim3(nq_pad), dim3(256), 0, st, q_dev, nq, h->dim, h->ld, w.qp, w.invq);

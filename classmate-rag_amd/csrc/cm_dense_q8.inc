@@ -18,33 +18,27 @@
 // is ~800 rows per query for the bench's E5 queries (a global max||e_r|| gives ~4,000),
 // tools/int8_band.py, profiles/r04_int8_band_rowE.json.
 //
-// Pipeline (launch_coarse, kind CM_DENSE_Q8): dense_prep_q8 -> K1q MINONLY over a 1/8 row sample
-// (per group: min of d~ + E_r) -> seed = the k-th smallest group minimum (>= the true k-th
-// distance) -> K1q: every live + allowed row with d~ - E_r <= seed into its (range, query) buffer
-// -> dense_rerank_q8_kernel: kth_up = k-th smallest d~ + E_r over the candidates, band = the
-// candidates with d~ - E_r <= kth_up (it holds every exact top-k row), exact fp64 re-rank of the
-// band from the fp32 rows.  A query whose buffer overflows or whose band exceeds kQBand goes to the
-// exact fp32 K1 pass, as K1c's.
+// Pipeline (launch_coarse, kind CM_DENSE_Q8): dense_prep_q8 -> f16 sample seed: K1c MINONLY over a
+// 1/16 row sample of the f16 plane (per group: min coarse distance), seed = the k-th smallest group
+// minimum + K1c's bound E (>= the true k-th distance) -> K1q, the int8 scan: every live + allowed
+// row with d~ - E_r <= seed into its (range, query) buffer -> dense_rerank_q8_kernel, three stages:
+// kth_up = k-th smallest d~ + E_r over the candidates and the int8 band = the candidates with
+// d~ - E_r <= kth_up (it holds every exact top-k row); the f16 band = its rows still certifiable
+// after re-scoring from the f16 plane (skipped when only the plane's sample prefix is held); exact
+// fp64 re-rank of that band from the fp32 rows ->
+// dense_rerank_wide_kernel for the queries whose band exceeds kQBand with complete candidate
+// buffers.  A query whose buffer overflows (or that the wide re-rank cannot hold) goes to the exact
+// fp32 K1 pass, as K1c's.  K1q-s (kind CM_DENSE_Q8S) is the same with K1s MINONLY as the sample
+// pass and dense_q8_stream_kernel as the scan.
 
-// k order inside a 64-k block: K1Q_MAP 1 gives lane group g the bytes k = 16 g .. 16 g + 15, 2 gives
-// it k = 8 g .. + 7 and 32 + 8 g .. + 7.  Either is exact (tools/mfma_i8_probe.hip, with integer
-// data: a k permutation applied to both operands leaves every dot product unchanged), because rows
-// and queries are packed through the same q8_ge.
-#ifndef K1Q_MAP
-#define K1Q_MAP 1
-#endif
+// k order inside a 64-k block: lane group g holds the bytes k = 16 g .. 16 g + 15.  Rows and queries
+// are packed through the same q8_ge, so the order is exact whatever it is (a k permutation applied
+// to both operands leaves every dot product unchanged; tools/mfma_i8_probe.hip).
 #ifndef K1Q_RING
 #define K1Q_RING 12
 #endif
 #ifndef K1Q_DBG
 #define K1Q_DBG 0  // timing ablations only (tools/build_dense_variant.sh -DK1Q_DBG=<bits>); product: 0
-#endif
-// 1: the corpus chunks travel HBM -> VGPRs (global_load_dwordx4 nt, KC chunks in flight per wave) ->
-// LDS (ds_write_b128, two chunks ahead of their use) instead of LDS-DMA; the tile metadata stays
-// LDS-DMA.  The DMA-source ablation (profiles/r06_k1q_dma_source_abl.txt) prices the LDS-DMA pieces
-// at ~0.5 ms of the loop whether they read HBM or L2: the cost is their issue, not the stream.
-#ifndef K1Q_VREG
-#define K1Q_VREG 0
 #endif
 constexpr int kQDbg = K1Q_DBG;  // 2 no candidate stores | 16 staged entries dropped | 32 no append loop | 64 no staging | 128 no epilogue | 1024 no DMA in the loop | 4096 no MFMA | 8192 L2-resident source
 constexpr int kQRing = K1Q_RING;  // LDS ring slots of 8 KiB (one 64 x 128 chunk each)
@@ -65,7 +59,6 @@ constexpr int kQBand = K1Q_RR;       // int8-band rows per query (Gaussian queri
 constexpr int kQBand2 = K1Q_RR / 2;  // f16-band rows per query the fp64 stage re-scores (~30 at the bench shape)
 constexpr int kQRT = K1Q_RT, kQRW = K1Q_RT / 64;   // re-rank threads / waves per query
 constexpr int kQSel = 256;        // rows at or below the band's k-th distance ranked for the output
-constexpr int kQSampleFrac = 8;   // seed sample: 1/8 of the rows
 constexpr int kQMeta = 4;         // LDS slots of 1 KiB for the tiles' row scales + live / allow words
 // K1q's LDS budget: ring + metadata slots + staging + counters, in two footprints.  The full 160 KiB
 // (the most staging: fewest processing passes) when the scan has the GPU to itself; 131 KiB when the
@@ -91,18 +84,8 @@ constexpr int q8_vm_after(int y, int z) {
 typedef int i32x4q __attribute__((ext_vector_type(4)));
 
 __host__ __device__ inline void q8_ge(int k6, int &g, int &e) {
-#if K1Q_MAP == 1
   g = k6 >> 4;
   e = k6 & 15;
-#else
-  if (k6 < 32) {
-    g = k6 >> 3;
-    e = k6 & 7;
-  } else {
-    g = (k6 - 32) >> 3;
-    e = 8 + ((k6 - 32) & 7);
-  }
-#endif
 }
 __host__ __device__ inline int64_t q8_plane_off(int64_t row, int k, int ld) {
   const int64_t tile = row >> 6;
@@ -257,9 +240,8 @@ __global__ void __launch_bounds__(256) dense_prep_q8(const float *__restrict__ q
 // A = s_q S, B = 1 - a_q - b_q E, W = 2 (a_q + b_q E) + 1e-6 (E >= e_r: valid, ~5 % looser than
 // the row's own e_r, which is nearly the group's under a shared scale), so one integer max3 tree
 // per (lane, q-tile) decides the whole lane:
-//   MINONLY: min over live rows of d~ + E_r <= B + W - A max acc  -> out_min;
-//   main:    no row of the lane passes lo_r <= seed unless B - A max acc <= seed (the same fp32
-//            expression, monotone in acc: exact, no margin).
+// no row of the lane passes lo_r <= seed unless B - A max acc <= seed (the same fp32 expression,
+// monotone in acc: exact, no margin).
 // That replaces ~4 VALU issues per (row, query) pair (v4/v5: the tests alone cost 0.5-0.9 ms of a
 // 1.15 ms scan, profiles/r04b_k1q_abl.txt).  A lane that passes stages one 96-B entry -- query,
 // live bits, first row, A, B, W, seed, its 16 raw products -- in the wave's LDS area; when the area
@@ -282,14 +264,14 @@ struct K1qLds {
   static_assert(total <= 160 * 1024 && stage_e >= 64, "K1q LDS: ring + metadata + staging + counters");
 };
 constexpr int kQLds = K1qLds<K1Q_LDS>::total, kQLdsShared = K1qLds<K1Q_LDS_SHARED>::total;
-template <bool MINONLY, int LDS = K1Q_LDS>
+template <int LDS = K1Q_LDS>
 __global__ void __launch_bounds__(256, 1)
     dense_q8_scan_kernel(const int8_t *__restrict__ Xq, const float2 *__restrict__ rmeta,
                          const uint32_t *__restrict__ live, const uint32_t *__restrict__ allow, int64_t n_words,
                          const int8_t *__restrict__ Qq, const float4 *__restrict__ qsc, int nq,
                          const float *__restrict__ seed, int64_t rows_per_wg, int64_t rows_end, int n_wg,
                          uint64_t *__restrict__ out_keys, float *__restrict__ out_up,
-                         uint32_t *__restrict__ out_cnt, float *__restrict__ out_min) {
+                         uint32_t *__restrict__ out_cnt) {
   constexpr int KC = 6, QT = 4, PCS = 2, RING = K1qLds<LDS>::ring;
   constexpr int kQStageE = K1qLds<LDS>::stage_e, kQCntOff = K1qLds<LDS>::cnt_off;
   static_assert(RING > KC + 1, "the tile's row scales must be younger than every chunk the tile waits for");
@@ -320,7 +302,7 @@ __global__ void __launch_bounds__(256, 1)
 #pragma unroll
       for (int qt = 0; qt < QT; ++qt) asm volatile("" : "+a"(qf[c][kh][qt]));
   // per q-tile constants of the lane's query: s_q, 1 - a_q, a_q, b_q, seed (-inf when padded)
-  float sq[QT], oaq[QT], aq[QT], bq[QT], sdq[QT], best[QT];
+  float sq[QT], oaq[QT], aq[QT], bq[QT], sdq[QT];
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
     const int qq = qp * kBQPass + qc0 + qt * 16 + j;
@@ -329,8 +311,7 @@ __global__ void __launch_bounds__(256, 1)
     aq[qt] = v.y;
     oaq[qt] = 1.0f - v.y;
     bq[qt] = v.z;
-    best[qt] = __builtin_inff();
-    sdq[qt] = MINONLY ? 0.f : (qq < nq ? seed[qq] : -__builtin_inff());
+    sdq[qt] = qq < nq ? seed[qq] : -__builtin_inff();
   }
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), seen by the compiler's wait tracking
   const __attribute__((address_space(1))) unsigned char *Xb = (const __attribute__((address_space(1))) unsigned char *)Xq;
@@ -361,24 +342,7 @@ __global__ void __launch_bounds__(256, 1)
     const int o = 4 * i + wave;
     __builtin_amdgcn_global_load_lds(Xb + (((cb + gl) * 8 + o) << 10) + lane * 16,
                                      (__attribute__((address_space(3))) void *)(lds + (gc % RING) * 8192 + o * 1024),
-                                     16, 0, K1C_AUX);
-  };
-  // K1Q_VREG: chunk gc's two pieces of this wave into registers / from registers into its LDS slot.
-  // Both in inline asm: a compiler-visible load makes the compiler guard the register's next use with
-  // its own wait, and across the tile loop's back-edge that wait is vmcnt(0) -- every chunk in flight
-  // drained at every step.  The explicit counted wait before each step's barrier covers the LDS write.
-  auto vsrc = [&](int gc, int i) __attribute__((always_inline)) {
-    const int gl = min(gc, total - 1);               // clamped: one control path past the end
-    return Xb + (((cb + gl) * 8 + 4 * i + wave) << 10) + lane * 16;
-  };
-  auto vload = [&](int gc, i32x4q (&v)[PCS]) __attribute__((always_inline)) {
-    asm volatile("global_load_dwordx4 %0, %2, off nt\n\tglobal_load_dwordx4 %1, %3, off nt"
-                 : "+v"(v[0]), "+v"(v[1]) : "v"(vsrc(gc, 0)), "v"(vsrc(gc, 1)) : "memory");
-  };
-  auto vstore = [&](int gc, const i32x4q (&v)[PCS]) __attribute__((always_inline)) {
-    const uint32_t a = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) unsigned char *)(
-        lds + (gc % RING) * 8192 + wave * 1024 + lane * 16);
-    asm volatile("ds_write_b128 %0, %1\n\tds_write_b128 %0, %2 offset:4096" ::"v"(a), "v"(v[0]), "v"(v[1]) : "memory");
+                                     16, 0, kK1cAux);
   };
   auto issue = [&](int gc, bool tile_start) __attribute__((always_inline)) {
 #pragma unroll
@@ -388,7 +352,7 @@ __global__ void __launch_bounds__(256, 1)
   auto frag = [&](int gc, int rt, int kh) -> i32x4q {
     return *reinterpret_cast<const i32x4q *>(lds + (gc % RING) * 8192 + (rt * 2 + kh) * 1024 + lane * 16);
   };
-  // main pass: this wave's staging (kQStageE entries of 96 B) and its 64 queries' candidate counters,
+  // this wave's staging (kQStageE entries of 96 B) and its 64 queries' candidate counters,
   // written and read through inline asm (plain LDS accesses here would make the compiler drain the
   // ring first)
   const uint32_t stg = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) unsigned char *)(
@@ -447,39 +411,18 @@ __global__ void __launch_bounds__(256, 1)
     }
     return 0u;
   };
-  if (!MINONLY) reinterpret_cast<uint32_t *>(lds + kQCntOff)[tid] = 0u;   // the 4 waves' counters
+  reinterpret_cast<uint32_t *>(lds + kQCntOff)[tid] = 0u;   // the 4 waves' counters
   i32x4q acc[4][QT];
 #pragma unroll
   for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) acc[rt][qt] = i32x4q{0, 0, 0, 0};
 
-  static_assert(!K1Q_VREG || PCS == 2, "K1Q_VREG: two pieces per wave and chunk");
-  // K1Q_VREG register ring: at step s (c = s % KC) vr[c] holds chunk s + 2, written to LDS after step s's
-  // barrier and refilled with chunk s + 2 + KC
-  i32x4q vr[K1Q_VREG ? KC : 1][PCS];
-#pragma unroll
-  for (int c = 0; c < (K1Q_VREG ? KC : 1); ++c) vr[c][0] = vr[c][1] = i32x4q{0, 0, 0, 0};
   if (total > 0) {
-    if constexpr (K1Q_VREG) {
-      // chunks 0, 1 by LDS-DMA (+ tile 0's metadata), chunks 2 .. KC + 1 into vr (+ tile 1's metadata
-      // after chunk KC's pieces, as every tile's metadata rides after its first chunk's loads)
-      issue(0, true);
-      issue(1, false);
-#pragma unroll
-      for (int c = 0; c < KC; ++c) {
-        vload(2 + c, vr[c]);
-        if ((2 + c) % KC == 0) issue_meta((2 + c) / KC);
-      }
-      // chunks 0, 1 landed: everything but the 2 KC loads and one metadata DMA younger than them
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * KC + 1) : "memory");
-      __builtin_amdgcn_s_barrier();
-    } else {
 #pragma unroll
     for (int p = 0; p < RING; ++p) issue(p, p % KC == 0);
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(q8_vm_after(0, RING - 1)) : "memory");
     __builtin_amdgcn_s_barrier();
-    }
     // Interleaved chunk schedule (K1c's, dense_coarse_scan_kernel): with one wave per SIMD nothing
     // hides a non-MFMA instruction but the MFMA issued before it, so every LDS read, the counted
     // wait, the barrier and the DMA pieces of a chunk are threaded one per MFMA gap
@@ -563,21 +506,11 @@ __global__ void __launch_bounds__(256, 1)
       __builtin_amdgcn_sched_barrier(0);                                                                              \
       if (m < 4) xf[2 + (m >> 1)][m & 1] = frag((gcv), 2 + (m >> 1), m & 1);                                          \
       if (m == W0) {                                                                                                  \
-        if constexpr (K1Q_VREG) /* chunk s + 2's loads landed (younger: the loads of steps s - 5 .. s - 1 and the */ \
-          /* one metadata DMA of steps s - 6 .. s - 1); this wave's LDS writes of chunk s + 1 retired */              \
-          asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * (KC - 1) + 1) : "memory");                          \
-        else                                                                                                          \
-          asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(q8_vm_after((cc) + 1, (cc) + RING - 1)) : "memory");    \
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(q8_vm_after((cc) + 1, (cc) + RING - 1)) : "memory");      \
         __builtin_amdgcn_s_barrier();                                                                                 \
       }                                                                                                               \
-      if constexpr (K1Q_VREG) {                                                                                       \
-        if (m == W0 + 1) vstore((gcv) + 2, vr[cc]);                                                                   \
-        if (m == W0 + 2) vload((gcv) + 2 + KC, vr[cc]);                                                               \
-        if (m == W0 + 3 && ((cc) + 2) % KC == 0) issue_meta(((gcv) + 2 + KC) / KC);                                   \
-      } else {                                                                                                        \
       if (!(kQDbg & 1024) && m > W0 && m <= W0 + PCS) issue_piece((gcv) + RING, m - W0 - 1);                          \
       if (!(kQDbg & 1024) && m == W0 + PCS + 1 && ((cc) + RING) % KC == 0) issue_meta(((gcv) + RING) / KC);           \
-      }                                                                                                               \
       __builtin_amdgcn_sched_barrier(0);                                                                              \
     }                                                                                                                 \
     _Pragma("unroll") for (int m = 0; m < 16; ++m) {                                                                  \
@@ -630,10 +563,6 @@ __global__ void __launch_bounds__(256, 1)
         const float A = sq[qt] * S, B = fmaf(-bq[qt], E, oaq[qt]);
         const float W = 2.0f * fmaf(bq[qt], E, aq[qt]) + 1e-6f;
         const float lmin = fmaf(-A, (float)amax[qt], B);    // the lane's smallest lo_r
-        if (MINONLY) {
-          if (amax[qt] != INT32_MIN) best[qt] = fminf(best[qt], lmin + W);
-          continue;
-        }
         const bool pass = lmin <= sdq[qt] && amax[qt] != INT32_MIN;
         const uint64_t P = __ballot(pass);
         if (kQDbg & 64) {                            // ablation: pre-test kept alive, nothing staged
@@ -673,22 +602,12 @@ __global__ void __launch_bounds__(256, 1)
     }
 #undef K1Q_STEP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // clamped tail DMAs land before the LDS is released
-    if (!MINONLY && nst) nst = process(nst);
+    if (nst) nst = process(nst);
   }
-  if (MINONLY) {
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt) {
-      float m = best[qt];
-      m = fminf(m, __shfl_xor(m, 16));
-      m = fminf(m, __shfl_xor(m, 32));
-      if (g == 0) out_min[((int64_t)qp * n_wg + wg) * kBQPass + qc0 + qt * 16 + j] = m;
-    }
-  } else {
-    uint32_t c;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(c) : "v"(cnt_lds + lane * 4) : "memory");
-    if ((kQDbg & (64 | 128)) && dbg_sink == 0x7fffffffu) c = 0u;   // keeps the ablations' work observable
-    out_cnt[qbuf0 + lane] = c;
-  }
+  uint32_t c;
+  asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(c) : "v"(cnt_lds + lane * 4) : "memory");
+  if ((kQDbg & (64 | 128)) && dbg_sink == 0x7fffffffu) c = 0u;   // keeps the ablations' work observable
+  out_cnt[qbuf0 + lane] = c;
 }
 
 // K1q-s: the int8 scan for nq <= kSQ queries (single queries and small batches: north_star's
@@ -1135,9 +1054,6 @@ __global__ void __launch_bounds__(kQRT) dense_rerank_q8_kernel(
     return;
   }
   }   // Xh != nullptr (without it: s_ex = g_key's 64 KiB holds kQBand keys beside s_rows in g_up's space)
-#ifdef K1Q_PRINT
-  if (tid == 0 && (qi % 32) == 0) printf("rerank q %d: candidates %d band %d band2 %d\n", qi, total, band, band2);
-#endif
   const double qnrm = (double)qsc[qi].w;
   // ld = 768: 12 strided elements per lane, loaded unconditionally (rows are zero past dim, and so
   // is s_q: the extra terms add exact zeros, so the sums equal dense_rerank_kernel's over dim)

@@ -111,13 +111,14 @@ def test_dense_shapes(eng, n, nq, k, dim, path):
 
 
 @pytest.mark.parametrize("n,nq,k,dim", [(30000, 64, 24, 768), (12345, 100, 10, 384), (5000, 300, 32, 100),
-                                        (40000, 256, 1, 768), (257, 80, 32, 64)])
+                                        (40000, 256, 1, 768), (257, 80, 32, 64), (16448, 300, 10, 384)])
 @pytest.mark.parametrize("path", [2, 3, 4, 5, 6])
 def test_dense_batched_split_paths(eng, n, nq, k, dim, path):
     """K1c (coarse f16 scan, all queries of a pass resident) and K1s (<= 32 queries, per-wave
     streams), both + certified exact re-rank; path 2 (the retired K1b) means automatic:
     distances within 1e-4, sets/order as the oracle, deletes and filters honoured, multiple
-    query passes (nq > 256)."""
+    query passes (nq > 256).  (16448, 300, 10, 384): K1c's ld-384 instance over two passes, on
+    the smallest corpus (a multiple of 64 rows) the coarse kinds take."""
     rng = np.random.default_rng(n + nq + k)
     emb = rng.standard_normal((n, dim)).astype(np.float32) * rng.uniform(0.1, 10, (n, 1)).astype(np.float32)
     q = rng.standard_normal((nq, dim)).astype(np.float32)
@@ -125,6 +126,8 @@ def test_dense_batched_split_paths(eng, n, nq, k, dim, path):
     idx = eng.DenseIndex(dim)
     idx.set_path(path)
     idx.upsert(emb, np.arange(n))
+    if (n, dim, path) == (16448, 384, 3):
+        assert idx.search_kind(nq, k) == 3   # not the fp32 scan
     dist, rows = idx.search(q, k)
     _check_dense(dist, rows, emb, q, k)
     allow = rng.random(n) < 0.3
