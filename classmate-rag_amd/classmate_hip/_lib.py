@@ -69,6 +69,7 @@ SIGNATURES = {
     "cm_dense_size": (c_i64, c_vp),
     "cm_dense_dim": (c_i32, c_vp),
     "cm_dense_search": (c_int, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp),
+    "cm_dense_search_lists": (c_int, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp),
     "cm_dense_search_workspace": (c_i64, c_vp, c_i32, c_i32),
     "cm_dense_search_kind": (c_i32, c_vp, c_i32, c_i32),
     "cm_dense_set_path": (c_int, c_vp, c_i32),

@@ -188,6 +188,54 @@ class DenseIndex:
                                         L.ptr(vecs)), "cm_dense_search")
         return (dist, rows, vecs) if return_vectors else (dist, rows)
 
+    def search_lists(self, q: np.ndarray, k: int, allow_words, filter_of, return_vectors: bool = False):
+        """``search`` for a batch whose queries carry different where clauses (cm_dense_search_lists:
+        no scan, the allowed live rows of each clause are gathered from a row list; exact fp64
+        distances).  allow_words: (n_filters, words) bitmaps -- a numpy array, a device tensor, or a
+        sequence of ``where_bits`` outputs (host words or device tensors); filter_of: (nq,) the
+        bitmap of each query.  Same outputs as ``search``."""
+        qq = _c(np.atleast_2d(q), np.float32)
+        if qq.shape[1] != self.dim:
+            raise ValueError(f"query dim {qq.shape[1]} != index dim {self.dim}")
+        nq = qq.shape[0]
+        need = (self.size + 31) // 32
+        if isinstance(allow_words, (list, tuple)):
+            if not allow_words:
+                raise ValueError("allow_words holds no bitmap")
+            for w in allow_words:
+                if len(w.shape) != 1 or w.shape[0] < need:
+                    raise ValueError(f"allow bitmap has shape {tuple(w.shape)}, need ({need},) or longer")
+            if any(hasattr(w, "data_ptr") for w in allow_words):
+                dev = next(w.device for w in allow_words if hasattr(w, "data_ptr"))
+                ab = torch.stack([w[:need] if hasattr(w, "data_ptr") else
+                                  torch.from_numpy(_c(w, np.uint32)[:need].view(np.int32)).to(dev) for w in allow_words])
+            else:
+                ab = np.stack([_c(w, np.uint32)[:need] for w in allow_words])
+        else:
+            ab = allow_words
+            if len(ab.shape) != 2 or ab.shape[0] < 1 or ab.shape[1] < need:
+                raise ValueError(f"allow_words has shape {tuple(ab.shape)}, need (n_filters, {need}) or wider")
+            ab = ab[:, :need]
+        if need == 0:       # an empty store: nothing is read, but the pointer must not be NULL
+            ab = np.zeros((ab.shape[0], 1), np.uint32)
+        if hasattr(ab, "data_ptr"):     # rows of exactly `need` words
+            ab = ab.contiguous()
+            torch.cuda.current_stream(ab.device).synchronize()   # the copy above runs on torch's stream
+        else:
+            ab = _c(ab, np.uint32)
+        fo = _c(np.asarray(filter_of), np.int32)
+        if fo.shape != (nq,):
+            raise ValueError(f"filter_of has shape {fo.shape}, need ({nq},)")
+        if nq and (fo.min() < 0 or fo.max() >= ab.shape[0]):
+            raise ValueError(f"filter_of entries must be in [0, {ab.shape[0]})")
+        dist = np.empty((nq, k), np.float32)
+        rows = np.empty((nq, k), np.int64)
+        vecs = np.empty((nq, k, self.dim), np.float32) if return_vectors else None
+        if nq:
+            L.check(L.fn["cm_dense_search_lists"](self._h, L.ptr(qq), nq, int(k), L.ptr(ab), int(ab.shape[0]), L.ptr(fo),
+                                                  L.ptr(dist), L.ptr(rows), L.ptr(vecs)), "cm_dense_search_lists")
+        return (dist, rows, vecs) if return_vectors else (dist, rows)
+
     def export(self, row0: int = 0, n: Optional[int] = None, with_live: bool = False):
         """Host copy of rows [row0, row0+n) (and their live mask)."""
         n = self.size - row0 if n is None else int(n)

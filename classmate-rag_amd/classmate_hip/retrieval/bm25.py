@@ -637,9 +637,27 @@ class BM25Store:
         return self.search_batch(queries=[query], where=where, top_k=top_k)[0]
 
     @_locked
-    def search_batch(self, *, queries: Sequence[str], where: Optional[Mapping[str, Any]] = None,
-                     top_k: int = 8) -> List[List[Dict[str, Any]]]:
-        """Many queries sharing one filter: one device launch (build-side addition)."""
+    def search_batch(self, *, queries: Sequence[str], where=None, top_k: int = 8) -> List[List[Dict[str, Any]]]:
+        """Many queries: one device launch per filter (build-side addition).  ``where``: one clause (a
+        mapping or None) for the whole batch, or a list / tuple with one clause (or None / {}) per
+        query.  BM25 statistics are those of the filtered candidate set (quirk Q2), so the queries of
+        each distinct clause run the filtered search together and the results return in query order."""
+        if isinstance(where, (list, tuple)):
+            if len(where) != len(queries):
+                raise ValueError(f"where holds {len(where)} clauses for {len(queries)} queries")
+            from .vector_store import group_clauses
+            group_of, clauses = group_clauses(where)
+            out: List[List[Dict[str, Any]]] = [[] for _ in queries]
+            for g in sorted(set(group_of)):
+                sel = [i for i, x in enumerate(group_of) if x == g]
+                res = self._search_one_clause([queries[i] for i in sel], clauses[g] if g >= 0 else None, top_k)
+                for i, r in zip(sel, res):
+                    out[i] = r
+            return out
+        return self._search_one_clause(queries, where, top_k)
+
+    def _search_one_clause(self, queries: Sequence[str], where: Optional[Mapping[str, Any]],
+                           top_k: int) -> List[List[Dict[str, Any]]]:
         out: List[List[Dict[str, Any]]] = [[] for _ in queries]
         live = [i for i, q in enumerate(queries) if q.strip()]
         if not live or not self._entries:

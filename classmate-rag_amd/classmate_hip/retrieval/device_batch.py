@@ -64,6 +64,8 @@ def applicable(retr, filters, hybrid: bool) -> bool:
     vs, bm = retr.vector_store, retr.bm25_store
     if not hybrid or not retr.use_mmr:
         return False
+    if isinstance(filters, (list, tuple)):   # one filter per question: the host path groups them
+        return False
     if not isinstance(vs, GpuVectorStore) or not isinstance(bm, BM25Store):
         return False
     vs._ensure_loaded()

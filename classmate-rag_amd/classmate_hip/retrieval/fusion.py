@@ -202,8 +202,10 @@ class HybridRetriever:
         return self._merge(vec_res, bm25_res, top_k, hybrid)
 
     # ---- batched: one device launch per stage for the whole batch -----------------
-    def retrieve_batch(self, *, questions: Sequence[str], filters: Optional[Mapping[str, object]] = None,
+    def retrieve_batch(self, *, questions: Sequence[str], filters=None,
                        top_k: int = 8, hybrid: bool = True) -> List[List[Dict[str, object]]]:
+        """``filters``: one filter dict (or None) for the whole batch, or a list / tuple with one
+        filter dict (or None) per question."""
         with _stores_locked(self):
             return self._retrieve_batch(questions, filters, top_k, hybrid)
 
@@ -211,13 +213,23 @@ class HybridRetriever:
         questions = list(questions)
         if not questions:
             return []
-        raw_filters = filters or {}
-        if os.environ.get("CM_RETRIEVE_DEVICE", "1") != "0" and device_batch.applicable(self, raw_filters, hybrid):
-            out = device_batch.retrieve_batch(self, questions, top_k, raw_filters)   # whole batch on the device
-            if out is not None:
-                return out
-        chroma_where = build_where_filter(raw_filters) if raw_filters else None
-        bm_where = raw_filters or None
+        if isinstance(filters, (list, tuple)):
+            # one filter dict per question: the host path, build_where_filter per question (the stores
+            # group equal clauses); result i equals retrieve(question=questions[i], filters=filters[i])
+            if len(filters) != len(questions):
+                raise ValueError(f"filters holds {len(filters)} entries for {len(questions)} questions")
+            chroma_where = [build_where_filter(f) if f else None for f in filters]
+            bm_where = [f or None for f in filters]
+            if not (hasattr(self.vector_store, "query_batch") and hasattr(self.bm25_store, "search_batch")):
+                return [self._retrieve(q, f, top_k, hybrid) for q, f in zip(questions, filters)]
+        else:
+            raw_filters = filters or {}
+            if os.environ.get("CM_RETRIEVE_DEVICE", "1") != "0" and device_batch.applicable(self, raw_filters, hybrid):
+                out = device_batch.retrieve_batch(self, questions, top_k, raw_filters)   # whole batch on the device
+                if out is not None:
+                    return out
+            chroma_where = build_where_filter(raw_filters) if raw_filters else None
+            bm_where = raw_filters or None
         k = self.k_vector if hybrid else max(top_k, self.k_vector)
         q_vecs = self.embedder.encode_queries(questions)
         pool = max(k, self.mmr_max_pool) if self.use_mmr else k

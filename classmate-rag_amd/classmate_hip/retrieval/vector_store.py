@@ -53,6 +53,93 @@ from .filters import MetaIndex, next_uid, settle_loaded
 
 _FORMAT = 2
 
+# query_batch(where=[...]): a clause that allows more than size / LIST_CUTOFF_DIV rows is searched
+# by the ordinary scan, once per distinct clause; more selective ones share one row-list search
+# (engine.DenseIndex.search_lists).  In bytes the two tie at size / 4 for one clause (4 * ld per
+# allowed row against ld per store row of the int8 plane); a factor of 2 is kept back for the
+# compaction and the sort; measured (profiles/dense_lists.txt), one question per clause still wins at
+# size / 4, the largest share timed, and half of that is this value.  $CM_LIST_CUTOFF_DIV (read at
+# every call) overrides it and switches the pair rule below off: 1 sends every clause to the list
+# route, a value above the store's size none.
+LIST_CUTOFF_DIV = 8
+# (query, allowed row) pairs per search_lists call: 16 bytes of keys each, 64M pairs = 1 GiB
+LIST_PAIR_BUDGET = 64 << 20
+# The list route costs per (question, allowed row) pair, a scan per store row whatever the number of
+# questions that share its clause: a clause whose questions x allowed rows pass size / LIST_PAIR_DIV
+# takes the scan.  Measured (profiles/dense_lists.txt, 1M x 768): with 16 questions per clause the two
+# routes meet at 1.26 pairs per store row, with 256 per clause between 0.25 and 1.9; half the former.
+LIST_PAIR_DIV = 2
+
+
+def _list_cutoff_div() -> float:
+    return float(os.environ.get("CM_LIST_CUTOFF_DIV") or LIST_CUTOFF_DIV)
+
+
+def route_clauses(group_of: Sequence[int], counts: Sequence[int], size: int, top_k: int, max_topk: int,
+                  has_lists: bool, cutoff_div: float = LIST_CUTOFF_DIV, pair_budget: int = LIST_PAIR_BUDGET,
+                  pair_div: float = LIST_PAIR_DIV):
+    """Which search answers each query of a batch with per-query clauses (pure: no device, no store).
+
+    group_of[i] is the clause group of query i, or -1 without a clause; counts[g] the rows group g
+    allows.  Returns {"plain": queries without a clause (one ordinary search), "empty": queries whose
+    clause allows no row (their result is []), "scan": [(g, queries)] -- one ordinary filtered search
+    per clause: a clause allowing more than size / cutoff_div rows, a clause whose queries x allowed
+    rows pass size / pair_div, any request with top_k above max_topk, any index without
+    search_lists -- and "lists": [[(g, queries), ...], ...], one
+    search_lists call per inner list, split so that the sum over a call's queries of their clause's
+    count stays within pair_budget (a single query above it still gets a call of its own)}."""
+    plain, empty, by_group = [], [], {}
+    for i, g in enumerate(group_of):
+        if g < 0:
+            plain.append(i)
+        elif counts[g] <= 0:
+            empty.append(i)
+        else:
+            by_group.setdefault(g, []).append(i)
+    scan, lists, cur, pairs = [], [], [], 0
+    for g in sorted(by_group):
+        qs = by_group[g]
+        if (not has_lists or top_k > max_topk or counts[g] * cutoff_div > size
+                or counts[g] * len(qs) * pair_div > size):
+            scan.append((g, qs))
+            continue
+        for i in qs:
+            if cur and pairs + counts[g] > pair_budget:
+                lists.append(cur)
+                cur, pairs = [], 0
+            if cur and cur[-1][0] == g:
+                cur[-1][1].append(i)
+            else:
+                cur.append((g, [i]))
+            pairs += counts[g]
+    if cur:
+        lists.append(cur)
+    return {"plain": plain, "empty": empty, "scan": scan, "lists": lists}
+
+
+def group_clauses(wheres: Sequence[Optional[Mapping[str, Any]]]):
+    """(group_of, clauses): equal clauses -- device_batch._canon's typed canonical form, so key order
+    does not matter while True, 1 and "1" stay distinct -- share a group; a clause that form cannot
+    express is a group of its own; None and {} get -1."""
+    from .device_batch import _canon
+    group_of, clauses, seen = [], [], {}
+    for w in wheres:
+        if not w:
+            group_of.append(-1)
+            continue
+        try:
+            key = _canon(w)
+            g = seen.get(key)
+        except (TypeError, ValueError):
+            key = g = None
+        if g is None:
+            g = len(clauses)
+            clauses.append(w)
+            if key is not None:
+                seen[key] = g
+        group_of.append(g)
+    return group_of, clauses
+
 
 class _State:
     """The collection itself: device index, row <-> id tables, documents, metadata.  One per
@@ -544,10 +631,67 @@ class GpuVectorStore:
         vecs = res[2] if include_embeddings else None
         return self._items(dist, rows, vecs, 0, include_documents, include_embeddings, copy=True)
 
+    def _fit_words(self, words, need: int):
+        """An allow bitmap of at least ``need`` words (rows past the metadata are not allowed)."""
+        if words.shape[0] >= need:
+            return words
+        if hasattr(words, "data_ptr"):
+            import torch
+            return torch.cat([words, torch.zeros(need - words.shape[0], dtype=words.dtype, device=words.device)])
+        return np.concatenate([words, np.zeros(need - words.shape[0], words.dtype)])
+
+    def _query_batch_clauses(self, q: np.ndarray, wheres, top_k: int, include_documents: bool,
+                             include_embeddings: bool) -> List[List[Dict[str, Any]]]:
+        """query_batch with one where clause (or None / {}) per query: result i equals
+        query(where=wheres[i]) -- the same rows, exact distances on the list route."""
+        nq = q.shape[0]
+        if len(wheres) != nq:
+            raise ValueError(f"where holds {len(wheres)} clauses for {nq} queries")
+        if top_k is None or int(top_k) <= 0:
+            raise ValueError(f"Expected n_results to be a positive integer, got {top_k}")
+        top_k = int(top_k)
+        self._ensure_loaded()
+        out: List[List[Dict[str, Any]]] = [[] for _ in range(nq)]
+        if self._index is None:
+            return out
+        idx = self._index
+        group_of, clauses = group_clauses(wheres)
+        bits = [engine.where_bits(self._meta, w, "chroma", idx.device) for w in clauses]   # once per distinct clause
+        counts = [n for _, n in bits]
+        plan = route_clauses(group_of, counts, len(self._ids), top_k, engine.L.max_topk(),
+                             hasattr(idx, "search_lists"), _list_cutoff_div(), LIST_PAIR_BUDGET,
+                             0.0 if os.environ.get("CM_LIST_CUTOFF_DIV") else LIST_PAIR_DIV)   # forced: rows alone
+        need = (idx.size + 31) // 32
+
+        def fill(sel, res):
+            vecs = res[2] if include_embeddings else None
+            if vecs is not None:
+                vecs.setflags(write=False)
+            for j, i in enumerate(sel):
+                out[i] = self._items(res[0], res[1], vecs, j, include_documents, include_embeddings)
+
+        if plan["plain"]:
+            res = self._search(q[plan["plain"]], None, top_k, include_embeddings)
+            if res is not None:
+                fill(plan["plain"], res)
+        for g, sel in plan["scan"]:
+            fill(sel, idx.search(q[sel], min(top_k, counts[g]), bits[g][0], return_vectors=include_embeddings))
+        for call in plan["lists"]:
+            sel = [i for _, qs in call for i in qs]
+            filter_of = np.concatenate([np.full(len(qs), f, np.int32) for f, (_, qs) in enumerate(call)])
+            k = min(top_k, max(counts[g] for g, _ in call))
+            fill(sel, idx.search_lists(q[sel], k, [self._fit_words(bits[g][0], need) for g, _ in call], filter_of,
+                                       return_vectors=include_embeddings))
+        return out
+
     @_locked
-    def query_batch(self, *, query_embeddings: np.ndarray, where: Optional[Dict[str, Any]] = None, top_k: int = 8,
+    def query_batch(self, *, query_embeddings: np.ndarray, where=None, top_k: int = 8,
                     include_documents: bool = True, include_embeddings: bool = False) -> List[List[Dict[str, Any]]]:
+        """``where``: one clause (a mapping or None) for the whole batch, or a list / tuple with one
+        clause (or None / {}) per query."""
         q = np.atleast_2d(np.asarray(query_embeddings).astype("float32"))
+        if isinstance(where, (list, tuple)):
+            return self._query_batch_clauses(q, where, top_k, include_documents, include_embeddings)
         res = self._search(q, where, top_k, include_embeddings)
         if res is None:
             return [[] for _ in range(q.shape[0])]

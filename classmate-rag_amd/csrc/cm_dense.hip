@@ -2335,3 +2335,5 @@ int cm_dense_search(cm_dense *h, const float *q, int32_t nq, int32_t k, const ui
 
 // cm_dense_compact / cm_dense_truncate: reclaiming deleted rows
 #include "cm_dense_compact.inc"
+// cm_dense_search_lists: per-query where clauses answered from row lists, no scan
+#include "cm_dense_lists.inc"

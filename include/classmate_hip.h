@@ -121,6 +121,22 @@ int32_t cm_dense_dim(cm_dense *h);
  * output, complete before the call): ceil(size/32) words.               */
 int cm_dense_search(cm_dense *h, const float *q, int32_t nq, int32_t k, const uint32_t *allow_bits,
                     float *out_dist, int64_t *out_row, float *out_vec);
+/* ChromaVectorStore.query (rag/retrieval/vector_chroma.py:204-253) for a batch whose queries carry
+ * different where clauses.  allow_bits: n_filters bitmaps of ceil(size/32) words each, one after the
+ * other, host or device memory (as cm_dense_search's).  filter_of (host): nq entries in [0, n_filters).
+ * Query i gets the k nearest rows that are live and allowed by bitmap filter_of[i], in ascending
+ * (distance, row) order.  Distances use cm_dense_search's k > cm_max_topk formula:
+ * (float)(1 - c.q / ((|c| + 1e-30)(|q| + 1e-30))) in fp64.  Entries past the allowed live rows are
+ * row -1 with the pad distance cm_dense_search writes.  out_vec nullable, as cm_dense_search.
+ * Host function: runs on the handle's stream, may synchronise, returns when the outputs are written.
+ * No scan: the allowed live rows of every bitmap are compacted into a row list, and only those fp32
+ * rows are read, once per tile of 8 queries that share the list.  A null handle or argument, nq < 1,
+ * k < 1, n_filters < 1 and a filter_of entry outside [0, n_filters) -> CM_EINVAL, checked on the host
+ * before any device call; k > cm_max_topk(), or a batch with 2^31 or more (query, allowed row)
+ * pairs -> CM_EUNSUPPORTED; a failed workspace allocation -> CM_ENOMEM. */
+int cm_dense_search_lists(cm_dense *h, const float *q, int32_t nq, int32_t k, const uint32_t *allow_bits,
+                          int32_t n_filters, const int32_t *filter_of, float *out_dist, int64_t *out_row,
+                          float *out_vec);
 /* workspace bytes cm_dense_search_dev needs for (nq, k). */
 int64_t cm_dense_search_workspace(cm_dense *h, int32_t nq, int32_t k);
 /* which scan kernel cm_dense_search[_dev] runs for (nq, k): CM_DENSE_F32
