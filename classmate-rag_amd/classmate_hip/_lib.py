@@ -111,6 +111,8 @@ SIGNATURES = {
     "cm_bm25_term_stats": (c_int, c_vp, c_vp, c_vp),
     "cm_bm25_set_stats": (c_int, c_vp, c_vp, c_i32, c_i64, c_i64, c_f64),
     "cm_bm25_search": (c_int, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp),
+    "cm_bm25_search_lists": (c_int, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp),
+    "cm_bm25_last_eps_filters": (c_i32, c_vp),
     "cm_bm25_workspace_items": (c_i64, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64),
     "cm_bm25_workspace_subblocks": (c_i64, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64),
     "cm_bm25_timing_drain_block": (c_i32, c_vp, c_vp, c_i32),

@@ -73,6 +73,37 @@ class _StreamOwner:
             pass
 
 
+def _list_allow_words(allow_words, need: int):
+    """search_lists' bitmaps as one (n_filters, need) array of words, host (numpy uint32) or device
+    (a contiguous tensor): from a numpy array, a device tensor, or a sequence of ``where_bits``
+    outputs (host words or device tensors)."""
+    if isinstance(allow_words, (list, tuple)):
+        if not allow_words:
+            raise ValueError("allow_words holds no bitmap")
+        for w in allow_words:
+            if len(w.shape) != 1 or w.shape[0] < need:
+                raise ValueError(f"allow bitmap has shape {tuple(w.shape)}, need ({need},) or longer")
+        if any(hasattr(w, "data_ptr") for w in allow_words):
+            dev = next(w.device for w in allow_words if hasattr(w, "data_ptr"))
+            ab = torch.stack([w[:need] if hasattr(w, "data_ptr") else
+                              torch.from_numpy(_c(w, np.uint32)[:need].view(np.int32)).to(dev) for w in allow_words])
+        else:
+            ab = np.stack([_c(w, np.uint32)[:need] for w in allow_words])
+    else:
+        ab = allow_words
+        if len(ab.shape) != 2 or ab.shape[0] < 1 or ab.shape[1] < need:
+            raise ValueError(f"allow_words has shape {tuple(ab.shape)}, need (n_filters, {need}) or wider")
+        ab = ab[:, :need]
+    if need == 0:       # an empty store: nothing is read, but the pointer must not be NULL
+        ab = np.zeros((ab.shape[0], 1), np.uint32)
+    if hasattr(ab, "data_ptr"):     # rows of exactly `need` words
+        ab = ab.contiguous()
+        torch.cuda.current_stream(ab.device).synchronize()   # the copy above runs on torch's stream
+    else:
+        ab = _c(ab, np.uint32)
+    return ab
+
+
 class DenseIndex:
     """HBM-resident fp32 corpus + exact cosine top-k (replaces Chroma's HNSW)."""
 
@@ -199,30 +230,7 @@ class DenseIndex:
             raise ValueError(f"query dim {qq.shape[1]} != index dim {self.dim}")
         nq = qq.shape[0]
         need = (self.size + 31) // 32
-        if isinstance(allow_words, (list, tuple)):
-            if not allow_words:
-                raise ValueError("allow_words holds no bitmap")
-            for w in allow_words:
-                if len(w.shape) != 1 or w.shape[0] < need:
-                    raise ValueError(f"allow bitmap has shape {tuple(w.shape)}, need ({need},) or longer")
-            if any(hasattr(w, "data_ptr") for w in allow_words):
-                dev = next(w.device for w in allow_words if hasattr(w, "data_ptr"))
-                ab = torch.stack([w[:need] if hasattr(w, "data_ptr") else
-                                  torch.from_numpy(_c(w, np.uint32)[:need].view(np.int32)).to(dev) for w in allow_words])
-            else:
-                ab = np.stack([_c(w, np.uint32)[:need] for w in allow_words])
-        else:
-            ab = allow_words
-            if len(ab.shape) != 2 or ab.shape[0] < 1 or ab.shape[1] < need:
-                raise ValueError(f"allow_words has shape {tuple(ab.shape)}, need (n_filters, {need}) or wider")
-            ab = ab[:, :need]
-        if need == 0:       # an empty store: nothing is read, but the pointer must not be NULL
-            ab = np.zeros((ab.shape[0], 1), np.uint32)
-        if hasattr(ab, "data_ptr"):     # rows of exactly `need` words
-            ab = ab.contiguous()
-            torch.cuda.current_stream(ab.device).synchronize()   # the copy above runs on torch's stream
-        else:
-            ab = _c(ab, np.uint32)
+        ab = _list_allow_words(allow_words, need)
         fo = _c(np.asarray(filter_of), np.int32)
         if fo.shape != (nq,):
             raise ValueError(f"filter_of has shape {fo.shape}, need ({nq},)")
@@ -573,6 +581,37 @@ class BM25Index:
         L.check(L.fn["cm_bm25_search"](self._h, L.ptr(flat), L.ptr(off), nq, int(k), L.ptr(ab), L.ptr(scores),
                                        L.ptr(rows), L.ptr(nvalid)), "cm_bm25_search")
         return scores, rows, nvalid
+
+    def search_lists(self, queries: Sequence[Sequence[int]], k: int, allow_words, filter_of):
+        """``search`` for a batch whose queries carry different where clauses (cm_bm25_search_lists:
+        the allowed live rows of each clause are scored from a row list, with the clause's own
+        statistics; bit for bit what ``search([q], k, allow_words[filter_of[i]])`` returns per
+        query, for any k >= 1).  allow_words and filter_of as ``DenseIndex.search_lists``.  Same
+        outputs as ``search``."""
+        nq = len(queries)
+        off = np.zeros(nq + 1, np.int32)
+        for i, q in enumerate(queries):
+            off[i + 1] = off[i] + len(q)
+        flat = np.concatenate([np.asarray(q, np.int32) for q in queries]) if off[-1] else np.zeros(1, np.int32)
+        flat = _c(flat, np.int32)
+        ab = _list_allow_words(allow_words, (self.num_docs + 31) // 32)
+        fo = _c(np.asarray(filter_of), np.int32)
+        if fo.shape != (nq,):
+            raise ValueError(f"filter_of has shape {fo.shape}, need ({nq},)")
+        if nq and (fo.min() < 0 or fo.max() >= ab.shape[0]):
+            raise ValueError(f"filter_of entries must be in [0, {ab.shape[0]})")
+        scores = np.empty((nq, k), np.float64)
+        rows = np.empty((nq, k), np.int64)
+        nvalid = np.empty(nq, np.int32)
+        if nq:
+            L.check(L.fn["cm_bm25_search_lists"](self._h, L.ptr(flat), L.ptr(off), nq, int(k), L.ptr(ab), int(ab.shape[0]),
+                                                 L.ptr(fo), L.ptr(scores), L.ptr(rows), L.ptr(nvalid)),
+                    "cm_bm25_search_lists")
+        return scores, rows, nvalid
+
+    def last_eps_filters(self) -> int:
+        """Clauses of the last search_lists() that had a negative idf and took the epsilon pass."""
+        return int(L.fn["cm_bm25_last_eps_filters"](self._h))
 
     def workspace_bytes(self, nq: int, total_terms: int, k: int) -> int:
         n = int(L.fn["cm_bm25_search_workspace"](self._h, int(nq), int(total_terms), int(k)))

@@ -71,6 +71,21 @@ class _Entry:
 
 _SIDECAR_VERSION = 1
 
+# search_batch(where=[...]): vector_store.route_clauses under BM25's own constants.  A clause that
+# allows more than num_docs / BM25_LIST_CUTOFF_DIV rows, or whose questions x allowed rows pass
+# num_docs / BM25_LIST_PAIR_DIV, runs the ordinary filtered search once per clause; more selective
+# ones share row-list searches (engine.BM25Index.search_lists).  Measured (profiles/bm25_lists.txt,
+# 1M documents, medians of 30; DESIGN §3 "BM25 row-list search"), by the dense constants' rule -- half
+# of the largest measured share at which the list route still wins: with one question per clause it
+# wins at N/1024 (1.38 x) and N/64 (1.14 x), the largest share timed at 30 repetitions, so 128; with
+# 16 per clause it still wins at N/8 (1.05 x) = 2 pairs per document, so 1.  $CM_BM25_LIST_CUTOFF_DIV
+# (read at every call) overrides the first and switches the pair rule off: 1 sends every clause to
+# the list route, a value above the store's size none.
+BM25_LIST_CUTOFF_DIV = 128
+BM25_LIST_PAIR_DIV = 1
+# (query, allowed row) pairs per search_lists call: 24 bytes of keys and rows each, 32M pairs = 768 MiB
+BM25_LIST_PAIR_BUDGET = 32 << 20
+
 
 def _entry_of(rec: Mapping[str, Any]) -> _Entry:
     """bm25.py:240-245: one JSONL record -> _Entry."""
@@ -640,24 +655,74 @@ class BM25Store:
     def search_batch(self, *, queries: Sequence[str], where=None, top_k: int = 8) -> List[List[Dict[str, Any]]]:
         """Many queries: one device launch per filter (build-side addition).  ``where``: one clause (a
         mapping or None) for the whole batch, or a list / tuple with one clause (or None / {}) per
-        query.  BM25 statistics are those of the filtered candidate set (quirk Q2), so the queries of
-        each distinct clause run the filtered search together and the results return in query order."""
+        query.  BM25 statistics are those of the filtered candidate set (quirk Q2): selective clauses
+        share row-list searches that score each under its own statistics, the queries of any other
+        distinct clause run the filtered search together (_search_clauses); results in query order."""
         if isinstance(where, (list, tuple)):
             if len(where) != len(queries):
                 raise ValueError(f"where holds {len(where)} clauses for {len(queries)} queries")
-            from .vector_store import group_clauses
-            group_of, clauses = group_clauses(where)
-            out: List[List[Dict[str, Any]]] = [[] for _ in queries]
-            for g in sorted(set(group_of)):
-                sel = [i for i, x in enumerate(group_of) if x == g]
-                res = self._search_one_clause([queries[i] for i in sel], clauses[g] if g >= 0 else None, top_k)
-                for i, r in zip(sel, res):
-                    out[i] = r
-            return out
+            return self._search_clauses(queries, where, top_k)
         return self._search_one_clause(queries, where, top_k)
 
+    def _search_clauses(self, queries: Sequence[str], where, top_k: int) -> List[List[Dict[str, Any]]]:
+        """search_batch with one where clause (or None / {}) per query: result i equals
+        search(query=queries[i], where=where[i]).  Every distinct clause is evaluated once; the
+        selective ones (vector_store.route_clauses under BM25's constants) share row-list searches
+        (engine.BM25Index.search_lists, each clause with its own statistics: quirk Q2), the others --
+        and every clause of a negative top_k or of a sharded index -- run _search_one_clause."""
+        from .vector_store import group_clauses, route_clauses
+        group_of, clauses = group_clauses(where)
+        out: List[List[Dict[str, Any]]] = [[] for _ in queries]
+
+        bits = None
+
+        def per_clause(g, sel):
+            res = self._search_one_clause([queries[i] for i in sel], clauses[g] if g >= 0 else None, top_k,
+                                          bits[g] if bits and g >= 0 else None)
+            for i, r in zip(sel, res):
+                out[i] = r
+
+        groups = sorted(set(group_of))
+        if groups and groups[0] < 0:
+            per_clause(-1, [i for i, x in enumerate(group_of) if x < 0])
+        if not clauses or not self._entries:
+            return out
+        self._ensure_index()
+        idx = self._index
+        has_lists = hasattr(idx, "search_lists") and top_k >= 0
+        if has_lists:
+            self._ensure_meta()
+            bits = [engine.where_bits(self._meta, w, "bm25", idx.device) for w in clauses]   # once per distinct clause
+        # (without the list route the plan only groups: _search_one_clause evaluates its own clause)
+        counts = [n for _, n in bits] if bits else [1] * len(clauses)
+        forced = os.environ.get("CM_BM25_LIST_CUTOFF_DIV")
+        plan = route_clauses(group_of, counts, len(self._id_list), max(top_k, 0), 1 << 62, has_lists,
+                             float(forced or BM25_LIST_CUTOFF_DIV), BM25_LIST_PAIR_BUDGET,
+                             0.0 if forced else BM25_LIST_PAIR_DIV)   # forced: rows alone
+        for g, sel in plan["scan"]:
+            per_clause(g, sel)
+        for call in plan["lists"]:
+            sel = [i for _, qs in call for i in qs if queries[i].strip()]   # blank queries give []
+            if not sel:
+                continue
+            filter_of = np.concatenate([np.full(sum(1 for i in qs if queries[i].strip()), f, np.int32)
+                                        for f, (_, qs) in enumerate(call)])
+            k = min(top_k, max(counts[g] for g, _ in call))   # per clause min(top_k, Nc): nvalid
+            if k <= 0:
+                continue
+            qids = [self._query_ids(queries[i]) for i in sel]
+            scores, rows, nvalid = idx.search_lists(qids, k, [bits[g][0] for g, _ in call], filter_of)
+            for j, i in enumerate(sel):
+                out[i] = [self._hit(s, r) for s, r in zip(scores[j][: nvalid[j]], rows[j][: nvalid[j]])]
+        return out
+
+    def _hit(self, score, row) -> Dict[str, Any]:
+        e = self._entries[self._id_list[int(row)]]
+        return {"id": e.id, "document": e.text, "metadata": e.metadata, "score": float(score)}
+
     def _search_one_clause(self, queries: Sequence[str], where: Optional[Mapping[str, Any]],
-                           top_k: int) -> List[List[Dict[str, Any]]]:
+                           top_k: int, bits=None) -> List[List[Dict[str, Any]]]:
+        """``bits``: the clause's where_bits output, when the caller has evaluated it already."""
         out: List[List[Dict[str, Any]]] = [[] for _ in queries]
         live = [i for i, q in enumerate(queries) if q.strip()]
         if not live or not self._entries:
@@ -666,7 +731,7 @@ class BM25Store:
         allow = None
         if where:  # device-evaluated filter; statistics follow it (Q2)
             self._ensure_meta()
-            allow, n_cand = engine.where_bits(self._meta, where, "bm25", self._index.device)
+            allow, n_cand = bits or engine.where_bits(self._meta, where, "bm25", self._index.device)
         else:
             n_cand = len(self._id_list)
         if n_cand == 0:

@@ -1148,6 +1148,7 @@ struct cm_bm25 {
   double maxr_avgdl = 0.0;         // ... at this avgdl: a valid bound for every search avgdl <= it
   int32_t path = 0;                // 0 auto (pruned), 1 full K2 scan, 2 pruned
   int32_t last_rescored = 0;       // (query, range) pairs K2 re-scored in the last host search
+  int32_t last_eps_filters = 0;    // filters of the last cm_bm25_search_lists that took filtered_eps
   int32_t nhead = 0;
   int64_t npad = 0;
   int32_t lut_dmin = 0;                  // first doc length of K2's ratio table window
@@ -1770,6 +1771,7 @@ int bm25_finish_build(cm_bm25 *h, hipStream_t st) {
 #include "cm_bm25_append.inc"
 #include "cm_bm25_remove.inc"
 #include "cm_bm25_replace.inc"
+#include "cm_bm25_lists.inc"
 
 extern "C" {
 

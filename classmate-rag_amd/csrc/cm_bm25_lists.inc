@@ -1,0 +1,451 @@
+// BM25 row-list search (cm_bm25_search_lists; included by cm_bm25.hip): a batch whose queries carry
+// different where clauses (BM25Store.search, rag/retrieval/bm25.py:175-212, called once per question
+// by the reference).  cm_bm25_search answers one bitmap per call: a pass over all N/32 words for the
+// candidate statistics, a walk of every query term's whole posting list for its candidate df, the
+// pruned search.  A clause that allows a few thousand rows is answered here from its row list, and
+// every clause of the batch at once:
+//   1. lists  per (filter, word) popcount of allow[f][w] & live[w] (bits at or above ndocs ignored)
+//             and, in the same pass, the sum of dl over those rows (one atomic per workgroup); one
+//             exclusive scan (hipCUB) over all n_filters x n_words counts = the CSR offsets of every
+//             list; the lengths (Nc) and length sums are read back once; a scatter of the ascending
+//             row numbers.  (cm_dense_lists.inc step 1, restated: that file is another translation
+//             unit's, and its count pass has no length sum.)
+//   2. df     bm25_list_df_kernel: one workgroup per (filter-term, 256 rows of the filter's list);
+//             a thread looks its row up in the term (list_tf below), one atomic per wave.
+//   3. idf    L[Nc - df] - L[df] from the handle's log table (cm_bm25_prepare_filtered's: glibc
+//             logs, rank_bm25's bits); filters with a negative idf take filtered_eps.
+//   4. score  bm25_list_score_kernel: one workgroup per (query, 256 rows of its filter's list), one
+//             candidate per thread, the query's terms in query order with bm25_scatter_term_kernel's
+//             operands: bm25_search_full's sums, hence the fused path's.
+//   5. top-k  one segmented radix sort (hipCUB, stable) of (score_key, row) over the queries'
+//             segments, whose input is in ascending row order; the first min(k, Nc) of each segment.
+// Quirk Q2 is why the statistics are per filter; quirk Q1 (zero scores pad in row order) is the
+// stable sort's.  No posting crosses to the host.
+
+namespace cm {
+
+constexpr int kBmListChunk = 256;   // rows of one list per workgroup (tests restate it)
+constexpr int kBmListSlots = 64;    // query term descriptors staged in LDS at a time
+
+__device__ inline uint32_t bm_list_word(const uint32_t *__restrict__ allow, const uint32_t *__restrict__ live,
+                                        int64_t ndocs, int64_t n_words, int64_t f, int64_t w) {
+  uint32_t bits = allow[f * n_words + w] & live[w];
+  const int64_t left = ndocs - w * 32;
+  if (left < 32) bits &= (1u << left) - 1u;
+  return bits;
+}
+
+// Workgroup b = (filter b / nbw, words [256 (b % nbw), ...)): cnt[f * n_words + w] = rows of word w
+// that filter f allows and that are live, among rows < ndocs; sum_len[f] += their lengths (zeroed by
+// the caller); cnt[n_filters * n_words] = 0 (the exclusive scan's last element = all list entries).
+__global__ void __launch_bounds__(256) bm25_list_count_kernel(const uint32_t *__restrict__ allow,
+                                                              const uint32_t *__restrict__ live,
+                                                              const int32_t *__restrict__ dl, int64_t ndocs,
+                                                              int64_t n_words, int64_t nbw, int64_t total,
+                                                              int64_t *__restrict__ cnt,
+                                                              unsigned long long *__restrict__ sum_len) {
+  __shared__ unsigned long long red[4];
+  const int64_t f = blockIdx.x / nbw, w = (blockIdx.x % nbw) * 256 + threadIdx.x;
+  unsigned long long sum = 0;
+  if (w < n_words) {
+    uint32_t bits = bm_list_word(allow, live, ndocs, n_words, f, w);
+    cnt[f * n_words + w] = __popc(bits);
+    while (bits) {
+      sum += (unsigned long long)dl[w * 32 + (__ffs(bits) - 1)];
+      bits &= bits - 1;
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) cnt[total] = 0;
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned long long s = red[0] + red[1] + red[2] + red[3];
+    if (s) atomicAdd(sum_len + f, s);
+  }
+}
+
+// off[f] = prefix[f * n_words] for f <= n_filters: where each list starts (CSR); the length sums
+// follow them in the same buffer, for the one read-back.
+__global__ void __launch_bounds__(256) bm25_list_offsets_kernel(const int64_t *__restrict__ prefix, int64_t n_words,
+                                                                int n_filters, int64_t *__restrict__ off) {
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  if (f <= n_filters) off[f] = prefix[(int64_t)f * n_words];
+}
+
+// rows[prefix[i] + j] = row of the j-th set bit of (filter, word) i: every list ascending.
+__global__ void __launch_bounds__(256) bm25_list_scatter_kernel(const uint32_t *__restrict__ allow,
+                                                                const uint32_t *__restrict__ live, int64_t ndocs,
+                                                                int64_t n_words, int64_t total,
+                                                                const int64_t *__restrict__ prefix,
+                                                                int32_t *__restrict__ rows) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int64_t w = i % n_words;
+  uint32_t bits = bm_list_word(allow, live, ndocs, n_words, i / n_words, w);
+  int64_t o = prefix[i];
+  while (bits) {
+    rows[o++] = (int32_t)(w * 32 + (__ffs(bits) - 1));
+    bits &= bits - 1;
+  }
+}
+
+// tf of (term, row), 0 when the row has no posting of the term.  A term that owns a head tile: the
+// tile's byte (terms with a tf >= 255 own none, so the byte is the tf).  Otherwise a binary search of
+// the term's postings, which ascend by row.  Both read what bm25_head_fill_kernel copied.
+__device__ inline uint32_t bm_list_tf(int32_t head, int64_t lo, int64_t hi, int32_t row,
+                                      const uint8_t *__restrict__ headtf, int64_t npad,
+                                      const int32_t *__restrict__ post_doc, const uint16_t *__restrict__ post_tf) {
+  if (head >= 0) return headtf[(int64_t)head * npad + row];
+  const int64_t p = lower_bound_doc(post_doc, lo, hi, row);
+  return (p < hi && post_doc[p] == row) ? (uint32_t)post_tf[p] : 0u;
+}
+
+// One work item of the df pass (filter-term ft, chunk of its filter's list) and of the score pass
+// (query, chunk of its filter's list).
+struct BmListItem {
+  int32_t id, chunk;
+};
+
+// df[ft] += rows of the chunk that hold the term (zeroed by the caller).
+__global__ void __launch_bounds__(256) bm25_list_df_kernel(
+    const BmListItem *__restrict__ items, const int32_t *__restrict__ ft_filter, const int32_t *__restrict__ ft_term,
+    const int32_t *__restrict__ rows, const int64_t *__restrict__ list_off, const int64_t *__restrict__ term_off,
+    const int32_t *__restrict__ head_id, const uint8_t *__restrict__ headtf, int64_t npad,
+    const int32_t *__restrict__ post_doc, const uint16_t *__restrict__ post_tf, unsigned long long *__restrict__ df) {
+  const BmListItem it = items[blockIdx.x];
+  const int32_t f = ft_filter[it.id], t = ft_term[it.id];
+  const int64_t lo = list_off[f], len = list_off[f + 1] - lo;
+  const int64_t e = (int64_t)it.chunk * kBmListChunk + threadIdx.x;
+  bool has = false;
+  if (e < len)
+    has = bm_list_tf(head_id ? head_id[t] : -1, term_off[t], term_off[t + 1], rows[lo + e], headtf, npad, post_doc,
+                     post_tf) > 0;
+  const unsigned long long m = __ballot(has);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(df + it.id, (unsigned long long)__popcll(m));
+}
+
+// idf[ft] = L[Nc - df] - L[df] over the filter's candidates, 0 for df 0; neg[f] = 1 when one of
+// filter f's is negative (it then takes the filter's epsilon, bm25_list_slots_kernel).
+__global__ void bm25_list_idf_kernel(int n_ft, const int32_t *__restrict__ ft_filter,
+                                     const int64_t *__restrict__ list_off, const unsigned long long *__restrict__ df,
+                                     const double *__restrict__ logtab, double *__restrict__ idf,
+                                     int32_t *__restrict__ neg) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_ft) return;
+  const int32_t f = ft_filter[i];
+  const int64_t nc = list_off[f + 1] - list_off[f], d = (int64_t)df[i];
+  double v = 0.0;
+  if (d > 0) {
+    v = logtab[nc - d] - logtab[d];
+    if (v < 0) neg[f] = 1;
+  }
+  idf[i] = v;
+}
+
+// What the score pass needs of one query term slot: the term's postings [lo, lo + n), its head
+// tile (-1: none) and its idf under the query's filter (0: unknown term or outside the candidate
+// vocabulary -- the slot is skipped).
+struct BmListSlot {
+  int64_t lo;
+  int32_t n, head;
+  double idf;
+};
+
+// slot_ft[i] = the filter-term of query term slot i, -1 for an unknown term.
+__global__ void bm25_list_slots_kernel(int n_slots, const int32_t *__restrict__ slot_ft,
+                                       const int32_t *__restrict__ ft_filter, const int32_t *__restrict__ ft_term,
+                                       const double *__restrict__ idf, const double *__restrict__ eps,
+                                       const int64_t *__restrict__ term_off, const int32_t *__restrict__ head_id,
+                                       BmListSlot *__restrict__ slots) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_slots) return;
+  const int32_t ft = slot_ft[i];
+  BmListSlot s{0, 0, -1, 0.0};
+  if (ft >= 0) {
+    const int32_t t = ft_term[ft];
+    s.lo = term_off[t];
+    s.n = (int32_t)(term_off[t + 1] - s.lo);   // a term's postings are at most ndocs < 2^31
+    s.head = head_id ? head_id[t] : -1;
+    s.idf = idf[ft] < 0 ? eps[ft_filter[ft]] : idf[ft];
+  }
+  slots[i] = s;
+}
+
+// The hot kernel.  256 threads, one candidate each; the query's term descriptors pass through LDS
+// kBmListSlots at a time (block-uniform loop bounds and skips).  Per candidate: s = 0, then
+// s = s + bm25_contrib(idf, tf, kd_of(dl[row], avgdl_f)) for every slot with tf > 0 in query order --
+// bm25_scatter_term_kernel's operands and order.  The tf is looked up again per slot (bm_list_tf),
+// never stored.  Key and row of list element e go to the query's segment at e: ascending rows.
+__global__ void __launch_bounds__(256) bm25_list_score_kernel(
+    const BmListItem *__restrict__ items, const int32_t *__restrict__ filter_of, const int32_t *__restrict__ seg_off,
+    const int32_t *__restrict__ q_off, const BmListSlot *__restrict__ slots, const int32_t *__restrict__ rows,
+    const int64_t *__restrict__ list_off, const double *__restrict__ avgdl, const int32_t *__restrict__ dl,
+    const uint8_t *__restrict__ headtf, int64_t npad, const int32_t *__restrict__ post_doc,
+    const uint16_t *__restrict__ post_tf, uint64_t *__restrict__ keys, int32_t *__restrict__ vals) {
+  __shared__ BmListSlot s_slot[kBmListSlots];
+  const BmListItem it = items[blockIdx.x];
+  const int32_t f = filter_of[it.id];
+  const int64_t lo = list_off[f], len = list_off[f + 1] - lo;
+  const int64_t e = (int64_t)it.chunk * kBmListChunk + threadIdx.x;
+  const bool active = e < len;
+  const int32_t row = active ? rows[lo + e] : 0;
+  const double kd = active ? kd_of(dl[row], avgdl[f]) : 1.0;
+  double s = 0.0;
+  const int tb = q_off[it.id], te = q_off[it.id + 1];
+  for (int c0 = tb; c0 < te; c0 += kBmListSlots) {
+    const int n = min(kBmListSlots, te - c0);
+    __syncthreads();
+    if ((int)threadIdx.x < n) s_slot[threadIdx.x] = slots[c0 + threadIdx.x];
+    __syncthreads();
+    for (int j = 0; j < n; ++j) {
+      const BmListSlot d = s_slot[j];
+      if (d.idf == 0.0 || !active) continue;
+      const uint32_t tf = bm_list_tf(d.head, d.lo, d.lo + d.n, row, headtf, npad, post_doc, post_tf);
+      if (tf > 0) s = s + bm25_contrib(d.idf, tf, kd);
+    }
+  }
+  if (active) {
+    keys[(int64_t)seg_off[it.id] + e] = score_key(s);
+    vals[(int64_t)seg_off[it.id] + e] = row;
+  }
+}
+
+// out[i][j] = the j-th entry of query i's sorted segment; (0.0, -1) past its end.
+__global__ void __launch_bounds__(256) bm25_list_topk_kernel(const uint64_t *__restrict__ sorted,
+                                                             const int32_t *__restrict__ sorted_row,
+                                                             const int32_t *__restrict__ seg_off, int nq, int k,
+                                                             double *__restrict__ out_score,
+                                                             int64_t *__restrict__ out_row) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)nq * k) return;
+  const int i = (int)(idx / k), j = (int)(idx - (int64_t)i * k);
+  const int32_t s0 = seg_off[i];
+  if (j < seg_off[i + 1] - s0) {
+    out_score[idx] = f64_unorder(~sorted[(int64_t)s0 + j]);
+    out_row[idx] = (int64_t)sorted_row[(int64_t)s0 + j];
+  } else {
+    out_score[idx] = 0.0;
+    out_row[idx] = -1;
+  }
+}
+
+}  // namespace cm
+
+extern "C" {
+
+int cm_bm25_search_lists(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_off, int32_t nq, int32_t k,
+                         const uint32_t *allow_bits, int32_t n_filters, const int32_t *filter_of, double *out_score,
+                         int64_t *out_row, int32_t *out_n) {
+  // ---- argument checks: host only, before any device call ----
+  if (!h) CM_FAIL(CM_EINVAL, "null handle");
+  if (nq < 1) CM_FAIL(CM_EINVAL, "cm_bm25_search_lists: nq must be >= 1");
+  if (k < 1) CM_FAIL(CM_EINVAL, "cm_bm25_search_lists: k must be >= 1");
+  if (n_filters < 1) CM_FAIL(CM_EINVAL, "cm_bm25_search_lists: n_filters must be >= 1");
+  if (!q_terms || !q_off || !allow_bits || !filter_of || !out_score || !out_row || !out_n)
+    CM_FAIL(CM_EINVAL, "NULL argument");
+  for (int i = 0; i < nq; ++i)
+    if (filter_of[i] < 0 || filter_of[i] >= n_filters)
+      CM_FAIL(CM_EINVAL, "cm_bm25_search_lists: filter_of[" + std::to_string(i) + "] = " +
+                             std::to_string(filter_of[i]) + " is outside [0, n_filters)");
+  if (q_off[0] < 0) CM_FAIL(CM_EINVAL, "bad q_off");
+  for (int i = 0; i < nq; ++i)
+    if (q_off[i + 1] < q_off[i]) CM_FAIL(CM_EINVAL, "q_off must be non-decreasing");
+  DeviceGuard dg(h->dev);
+  const int64_t ndocs = h->ndocs, nw = ceil_div(ndocs, 32), total = (int64_t)n_filters * nw;
+  if (total + 1 > INT32_MAX)
+    CM_FAIL(CM_EUNSUPPORTED, "cm_bm25_search_lists: n_filters x ceil(ndocs / 32) must stay below 2^31: split the batch");
+  const int32_t n_slots = q_off[nq];
+  h->last_eps_filters = 0;
+  int rc;
+  // ---- 1. lists: count + length sums, scan, one read-back ----
+  std::vector<int64_t> stat(2 * (size_t)n_filters + 1, 0);   // off[0 .. n_filters], then sum_len[0 .. n_filters)
+  int64_t *prefix = nullptr, *off_dev = nullptr;
+  if (total > 0) {
+    size_t scan_b = 0;
+    CM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, (const int64_t *)nullptr, (int64_t *)nullptr,
+                                            (int)(total + 1), h->stream));
+    const size_t cnt_b = (size_t)round_up((total + 1) * 8, 256);
+    const size_t stat_b = (size_t)round_up((int64_t)stat.size() * 8, 256);
+    if ((rc = h->allow_buf.ensure((size_t)total * 4))) return rc;
+    if ((rc = h->tmp.ensure(2 * cnt_b + stat_b + std::max<size_t>(scan_b, 16)))) return rc;
+    char *b = h->tmp.as<char>();
+    int64_t *cnt = reinterpret_cast<int64_t *>(b);
+    prefix = reinterpret_cast<int64_t *>(b + cnt_b);
+    off_dev = reinterpret_cast<int64_t *>(b + 2 * cnt_b);
+    unsigned long long *sum_dev = reinterpret_cast<unsigned long long *>(off_dev + n_filters + 1);
+    CM_HIP(hipMemcpyAsync(h->allow_buf.ptr, allow_bits, (size_t)total * 4, hipMemcpyDefault, h->stream));  // host or device
+    CM_HIP(hipMemsetAsync(sum_dev, 0, (size_t)n_filters * 8, h->stream));
+    const int64_t nbw = ceil_div(nw, 256);
+    hipLaunchKernelGGL(bm25_list_count_kernel, dim3((unsigned)(nbw * n_filters)), dim3(256), 0, h->stream,
+                       h->allow_buf.as<uint32_t>(), h->live.as<uint32_t>(), h->dl.as<int32_t>(), ndocs, nw, nbw, total,
+                       cnt, sum_dev);
+    CM_HIP(hipGetLastError());
+    CM_HIP(hipcub::DeviceScan::ExclusiveSum(b + 2 * cnt_b + stat_b, scan_b, cnt, prefix, (int)(total + 1), h->stream));
+    hipLaunchKernelGGL(bm25_list_offsets_kernel, dim3((unsigned)ceil_div(n_filters + 1, 256)), dim3(256), 0, h->stream,
+                       prefix, nw, n_filters, off_dev);
+    CM_HIP(hipGetLastError());
+    CM_HIP(hipMemcpyAsync(stat.data(), off_dev, stat.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    CM_HIP(hipStreamSynchronize(h->stream));
+  }
+  const int64_t *off = stat.data(), *sum_len = stat.data() + n_filters + 1;
+  const int64_t n_rows = off[n_filters];
+  // ---- the queries' segments (host) ----
+  std::vector<int32_t> seg((size_t)nq + 1, 0);
+  std::vector<uint8_t> used((size_t)n_filters, 0);
+  int64_t n_keys = 0;
+  for (int i = 0; i < nq; ++i) {
+    const int f = filter_of[i];
+    const int64_t nc = off[f + 1] - off[f];
+    if (nc > 0 && sum_len[f] == 0)
+      CM_FAIL(CM_EZERODIV, "float division by zero (candidate documents have no tokens)");
+    n_keys += nc;
+    if (n_keys > INT32_MAX)
+      CM_FAIL(CM_EUNSUPPORTED, "cm_bm25_search_lists: more than 2^31 (query, row) pairs: split the batch");
+    seg[i + 1] = (int32_t)n_keys;
+    used[f] = 1;
+    out_n[i] = (int32_t)std::min<int64_t>(k, nc);
+  }
+  // ---- (filter, distinct known term) pairs of the queries that use the filter, and every slot's ----
+  std::vector<int32_t> slot_ft((size_t)std::max(n_slots, 1), -1);
+  std::vector<uint64_t> ftkey;
+  for (int i = 0; i < nq; ++i) {
+    if (off[filter_of[i] + 1] == off[filter_of[i]]) continue;   // nothing is scored under an empty list
+    for (int32_t j = q_off[i]; j < q_off[i + 1]; ++j)
+      if (q_terms[j] >= 0 && q_terms[j] < h->vocab) ftkey.push_back(((uint64_t)filter_of[i] << 32) | (uint32_t)q_terms[j]);
+  }
+  std::sort(ftkey.begin(), ftkey.end());
+  ftkey.erase(std::unique(ftkey.begin(), ftkey.end()), ftkey.end());
+  const int64_t n_ft = (int64_t)ftkey.size();
+  std::vector<int32_t> ft_filter((size_t)n_ft), ft_term((size_t)n_ft);
+  std::vector<BmListItem> df_items, sc_items;
+  for (int64_t u = 0; u < n_ft; ++u) {
+    const int32_t f = (int32_t)(ftkey[u] >> 32);
+    ft_filter[u] = f;
+    ft_term[u] = (int32_t)(uint32_t)ftkey[u];
+    for (int64_t c = 0; c < ceil_div(off[f + 1] - off[f], kBmListChunk); ++c)
+      df_items.push_back(BmListItem{(int32_t)u, (int32_t)c});
+  }
+  for (int i = 0; i < nq; ++i) {
+    const int f = filter_of[i];
+    if (off[f + 1] == off[f]) continue;
+    for (int32_t j = q_off[i]; j < q_off[i + 1]; ++j)
+      if (q_terms[j] >= 0 && q_terms[j] < h->vocab)
+        slot_ft[j] = (int32_t)(std::lower_bound(ftkey.begin(), ftkey.end(), ((uint64_t)f << 32) | (uint32_t)q_terms[j]) -
+                               ftkey.begin());
+    for (int64_t c = 0; c < ceil_div(off[f + 1] - off[f], kBmListChunk); ++c)
+      sc_items.push_back(BmListItem{i, (int32_t)c});
+  }
+  if (df_items.size() > (size_t)INT32_MAX || n_ft > INT32_MAX)
+    CM_FAIL(CM_EUNSUPPORTED, "cm_bm25_search_lists: too many work items: split the batch");
+  std::vector<double> avgdl((size_t)n_filters, 1.0);   // (Nc == 0: nothing is scored)
+  for (int f = 0; f < n_filters; ++f)
+    if (off[f + 1] > off[f]) avgdl[f] = (double)sum_len[f] / (double)(off[f + 1] - off[f]);
+  // ---- workspace: laid out once, now that every size is known (ensure may move the buffer) ----
+  size_t sort_b = 0;
+  if (n_keys > 0)
+    CM_HIP(hipcub::DeviceSegmentedRadixSort::SortPairs(
+        nullptr, sort_b, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const int32_t *)nullptr, (int32_t *)nullptr,
+        (int)n_keys, nq, (const int32_t *)nullptr, (const int32_t *)nullptr, 0, 64, h->stream));
+  size_t o = (size_t)round_up((int64_t)std::max<size_t>(sort_b, 16), 256);
+  const auto take = [&o](int64_t bytes) {
+    const size_t at = o;
+    o += (size_t)round_up(std::max<int64_t>(bytes, 16), 256);
+    return at;
+  };
+  const size_t rows_o = take(n_rows * 4), dfi_o = take((int64_t)df_items.size() * 8);
+  const size_t sci_o = take((int64_t)sc_items.size() * 8), ftf_o = take(n_ft * 4), ftt_o = take(n_ft * 4);
+  const size_t df_o = take(n_ft * 8), idf_o = take(n_ft * 8), neg_o = take((int64_t)n_filters * 4);
+  const size_t eps_o = take((int64_t)n_filters * 8), avg_o = take((int64_t)n_filters * 8);
+  const size_t sft_o = take((int64_t)n_slots * 4), slots_o = take((int64_t)n_slots * (int64_t)sizeof(BmListSlot));
+  const size_t qoff_o = take(((int64_t)nq + 1) * 4), fof_o = take((int64_t)nq * 4), seg_o = take(((int64_t)nq + 1) * 4);
+  const size_t keys_o = take(n_keys * 8), skeys_o = take(n_keys * 8), vals_o = take(n_keys * 4), svals_o = take(n_keys * 4);
+  const size_t osc_o = take((int64_t)nq * k * 8), orow_o = take((int64_t)nq * k * 8);
+  if ((rc = h->ws.ensure(o))) return rc;
+  if (n_keys > 0 && (rc = bm25_grow_logtab(h, ndocs))) return rc;
+  char *base = h->ws.as<char>();
+  const auto at = [base](size_t x) { return base + x; };
+  int32_t *rows = reinterpret_cast<int32_t *>(at(rows_o));
+  BmListItem *dfi_dev = reinterpret_cast<BmListItem *>(at(dfi_o)), *sci_dev = reinterpret_cast<BmListItem *>(at(sci_o));
+  int32_t *ftf_dev = reinterpret_cast<int32_t *>(at(ftf_o)), *ftt_dev = reinterpret_cast<int32_t *>(at(ftt_o));
+  unsigned long long *df_dev = reinterpret_cast<unsigned long long *>(at(df_o));
+  double *idf_dev = reinterpret_cast<double *>(at(idf_o)), *eps_dev = reinterpret_cast<double *>(at(eps_o));
+  double *avg_dev = reinterpret_cast<double *>(at(avg_o));
+  int32_t *neg_dev = reinterpret_cast<int32_t *>(at(neg_o)), *sft_dev = reinterpret_cast<int32_t *>(at(sft_o));
+  BmListSlot *slots_dev = reinterpret_cast<BmListSlot *>(at(slots_o));
+  int32_t *qoff_dev = reinterpret_cast<int32_t *>(at(qoff_o)), *fof_dev = reinterpret_cast<int32_t *>(at(fof_o));
+  int32_t *seg_dev = reinterpret_cast<int32_t *>(at(seg_o));
+  uint64_t *keys = reinterpret_cast<uint64_t *>(at(keys_o)), *skeys = reinterpret_cast<uint64_t *>(at(skeys_o));
+  int32_t *vals = reinterpret_cast<int32_t *>(at(vals_o)), *svals = reinterpret_cast<int32_t *>(at(svals_o));
+  double *d_score = reinterpret_cast<double *>(at(osc_o));
+  int64_t *d_row = reinterpret_cast<int64_t *>(at(orow_o));
+  const int32_t *head_id = h->nhead ? h->head_id.as<int32_t>() : (const int32_t *)nullptr;
+  std::vector<double> eps((size_t)n_filters, 0.0);   // (host sources of async copies: alive until the last synchronise)
+  CM_HIP(hipMemcpyAsync(seg_dev, seg.data(), seg.size() * 4, hipMemcpyHostToDevice, h->stream));
+  if (n_keys > 0) {
+    CM_HIP(hipMemcpyAsync(qoff_dev, q_off, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, h->stream));
+    CM_HIP(hipMemcpyAsync(fof_dev, filter_of, (size_t)nq * 4, hipMemcpyHostToDevice, h->stream));
+    CM_HIP(hipMemcpyAsync(avg_dev, avgdl.data(), avgdl.size() * 8, hipMemcpyHostToDevice, h->stream));
+    CM_HIP(hipMemcpyAsync(sci_dev, sc_items.data(), sc_items.size() * 8, hipMemcpyHostToDevice, h->stream));
+    if (n_slots > 0) CM_HIP(hipMemcpyAsync(sft_dev, slot_ft.data(), (size_t)n_slots * 4, hipMemcpyHostToDevice, h->stream));
+    // ---- 1b. the lists ----
+    hipLaunchKernelGGL(bm25_list_scatter_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, h->stream,
+                       h->allow_buf.as<uint32_t>(), h->live.as<uint32_t>(), ndocs, nw, total, prefix, rows);
+    CM_HIP(hipGetLastError());
+    if (n_ft > 0) {
+      // ---- 2. candidate df ----
+      CM_HIP(hipMemcpyAsync(ftf_dev, ft_filter.data(), (size_t)n_ft * 4, hipMemcpyHostToDevice, h->stream));
+      CM_HIP(hipMemcpyAsync(ftt_dev, ft_term.data(), (size_t)n_ft * 4, hipMemcpyHostToDevice, h->stream));
+      CM_HIP(hipMemcpyAsync(dfi_dev, df_items.data(), df_items.size() * 8, hipMemcpyHostToDevice, h->stream));
+      CM_HIP(hipMemsetAsync(df_dev, 0, (size_t)n_ft * 8, h->stream));
+      CM_HIP(hipMemsetAsync(neg_dev, 0, (size_t)n_filters * 4, h->stream));
+      hipLaunchKernelGGL(bm25_list_df_kernel, dim3((unsigned)df_items.size()), dim3(256), 0, h->stream, dfi_dev, ftf_dev,
+                         ftt_dev, rows, off_dev, h->term_off.as<int64_t>(), head_id, h->headtf.as<uint8_t>(), h->npad,
+                         h->post_doc.as<int32_t>(), h->post_tf.as<uint16_t>(), df_dev);
+      CM_HIP(hipGetLastError());
+      // ---- 3. idf, and the epsilon of the filters that have a negative one ----
+      hipLaunchKernelGGL(bm25_list_idf_kernel, dim3((unsigned)ceil_div(n_ft, 256)), dim3(256), 0, h->stream, (int)n_ft,
+                         ftf_dev, off_dev, df_dev, h->logtab.as<double>(), idf_dev, neg_dev);
+      CM_HIP(hipGetLastError());
+      std::vector<int32_t> neg((size_t)n_filters, 0);
+      CM_HIP(hipMemcpyAsync(neg.data(), neg_dev, neg.size() * 4, hipMemcpyDeviceToHost, h->stream));
+      CM_HIP(hipStreamSynchronize(h->stream));
+      for (int f = 0; f < n_filters; ++f) {
+        if (!neg[f]) continue;
+        // (reads the filter's bitmap where it lies; writes obuf only)
+        if ((rc = filtered_eps(h, h->allow_buf.as<uint32_t>() + (int64_t)f * nw, off[f + 1] - off[f], &eps[f]))) return rc;
+        h->last_eps_filters += 1;
+      }
+      if (h->last_eps_filters)
+        CM_HIP(hipMemcpyAsync(eps_dev, eps.data(), eps.size() * 8, hipMemcpyHostToDevice, h->stream));
+    }
+    if (n_slots > 0) {
+      hipLaunchKernelGGL(bm25_list_slots_kernel, dim3((unsigned)ceil_div(n_slots, 256)), dim3(256), 0, h->stream,
+                         (int)n_slots, sft_dev, ftf_dev, ftt_dev, idf_dev, eps_dev, h->term_off.as<int64_t>(), head_id,
+                         slots_dev);
+      CM_HIP(hipGetLastError());
+    }
+    // ---- 4. scores ----
+    h->timer.begin(h->stream);
+    hipLaunchKernelGGL(bm25_list_score_kernel, dim3((unsigned)sc_items.size()), dim3(256), 0, h->stream, sci_dev, fof_dev,
+                       seg_dev, qoff_dev, slots_dev, rows, off_dev, avg_dev, h->dl.as<int32_t>(), h->headtf.as<uint8_t>(),
+                       h->npad, h->post_doc.as<int32_t>(), h->post_tf.as<uint16_t>(), keys, vals);
+    CM_HIP(hipGetLastError());
+    h->timer.end(h->stream);
+    // ---- 5. top-k ----
+    CM_HIP(hipcub::DeviceSegmentedRadixSort::SortPairs(base, sort_b, keys, skeys, vals, svals, (int)n_keys, nq, seg_dev,
+                                                       seg_dev + 1, 0, 64, h->stream));
+  }
+  hipLaunchKernelGGL(bm25_list_topk_kernel, dim3((unsigned)ceil_div((int64_t)nq * k, 256)), dim3(256), 0, h->stream, skeys,
+                     svals, seg_dev, nq, k, d_score, d_row);
+  CM_HIP(hipGetLastError());
+  CM_HIP(hipMemcpyAsync(out_score, d_score, (size_t)nq * k * 8, hipMemcpyDeviceToHost, h->stream));
+  CM_HIP(hipMemcpyAsync(out_row, d_row, (size_t)nq * k * 8, hipMemcpyDeviceToHost, h->stream));
+  CM_HIP(hipStreamSynchronize(h->stream));
+  h->last_rescored = -1;
+  return CM_OK;
+}
+
+int32_t cm_bm25_last_eps_filters(cm_bm25 *h) { return h ? h->last_eps_filters : -1; }
+
+}  // extern "C"

@@ -352,6 +352,28 @@ int cm_bm25_set_stats(cm_bm25 *h, const double *idf, int32_t vocab, int64_t n_li
  * out_n[i] = number of valid entries (min(k, #candidates)).               */
 int cm_bm25_search(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_off, int32_t nq, int32_t k,
                    const uint32_t *allow_bits, double *out_score, int64_t *out_row, int32_t *out_n);
+/* BM25Store.search for a batch whose queries carry different where clauses.  q_terms, q_off and
+ * the outputs as cm_bm25_search; allow_bits: n_filters bitmaps of ceil(ndocs/32) words each, one after
+ * the other, host or device memory; filter_of (host): nq entries in [0, n_filters).  Query i's
+ * result is bit for bit cm_bm25_search's for that query alone under bitmap filter_of[i]: scores,
+ * rows, out_n[i] = min(k, Nc) and the (0.0, -1) pads; descending score, ties -> lower row,
+ * zero-score candidates padding in row order (quirk Q1); statistics (Nc, avgdl, df, the epsilon
+ * floor) of each bitmap's own candidate set (quirk Q2).  Any k >= 1: the result is a full order.
+ * Host function: runs on the handle's stream, synchronises, returns when the outputs are written.
+ * No scan and no posting walk: the allowed live rows of every bitmap are compacted into a row list,
+ * and each (query, row) pair is scored outright, its tf looked up in the term's head tile or by a
+ * binary search of its postings; one segmented sort orders every query's candidates (DESIGN §3
+ * "BM25 row-list search").  Only a bitmap with a negative idf costs a pass over all postings (its
+ * epsilon); cm_bm25_last_eps_filters = how many of the last call's did (-1: null handle).
+ * A null handle or argument, nq < 1, k < 1, n_filters < 1, a filter_of entry outside [0, n_filters)
+ * and a decreasing q_off -> CM_EINVAL, checked on the host before any device call; 2^31 or more
+ * (query, allowed row) pairs, or n_filters x ceil(ndocs/32) words -> CM_EUNSUPPORTED; a bitmap some
+ * query uses whose candidates hold no tokens -> CM_EZERODIV (cm_bm25_search's message); a failed
+ * workspace allocation -> CM_ENOMEM.  The handle stays usable after every error. */
+int cm_bm25_search_lists(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_off, int32_t nq, int32_t k,
+                         const uint32_t *allow_bits, int32_t n_filters, const int32_t *filter_of,
+                         double *out_score, int64_t *out_row, int32_t *out_n);
+int32_t cm_bm25_last_eps_filters(cm_bm25 *h);
 /* cm_bm25_search with the caller's statistics instead of this index's: q_idf[total] = every
  * query term's idf (0 for terms outside the candidate vocabulary; ignored for ids outside
  * [0, vocab)), avgdl and n_cand of the candidate set; allow_bits (host or device words,
