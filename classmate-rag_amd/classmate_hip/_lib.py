@@ -124,6 +124,8 @@ SIGNATURES = {
     "cm_bm25_filter_stats_dev": (c_int, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp),
     "cm_bm25_filter_term_stats_dev": (c_int, c_vp, c_vp, c_vp, c_vp, c_vp),
     "cm_bm25_filter_eps": (c_int, c_vp, c_vp, P(c_f64)),
+    "cm_bm25_filter_eps_multi": (c_int, c_vp, c_vp, c_i32, c_vp),
+    "cm_bm25_last_eps_passes": (c_i32, c_vp),
     "cm_bm25_search_stats_dev": (c_int, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                  c_vp, c_vp, c_i64, c_vp),
     "cm_bm25_search_filtered_dev": (c_int, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,

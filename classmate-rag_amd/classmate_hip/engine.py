@@ -678,6 +678,19 @@ class BM25Index:
         L.check(L.fn["cm_bm25_filter_eps"](self._h, L.ptr(ab), C.byref(e)), "cm_bm25_filter_eps")
         return e.value
 
+    def filter_eps_multi(self, allow_words) -> np.ndarray:
+        """``filter_eps`` of every bitmap of allow_words (the forms ``search_lists`` takes), bit for
+        bit, with up to 32 bitmaps sharing one pass over the postings (cm_bm25_filter_eps_multi)."""
+        ab = _list_allow_words(allow_words, (self.num_docs + 31) // 32)
+        eps = np.zeros(int(ab.shape[0]), np.float64)
+        L.check(L.fn["cm_bm25_filter_eps_multi"](self._h, L.ptr(ab), int(ab.shape[0]), L.ptr(eps)),
+                "cm_bm25_filter_eps_multi")
+        return eps
+
+    def last_eps_passes(self) -> int:
+        """Postings passes the last filter_eps_multi() or search_lists() took for its epsilon floors."""
+        return int(L.fn["cm_bm25_last_eps_passes"](self._h))
+
     def search_stats_dev(self, q_terms, q_off, k: int, allow, stats, df, eps=None, out=None, status=None,
                          workspace=None):
         """Device search of the allowed documents with the given candidate statistics (device

@@ -1148,7 +1148,8 @@ struct cm_bm25 {
   double maxr_avgdl = 0.0;         // ... at this avgdl: a valid bound for every search avgdl <= it
   int32_t path = 0;                // 0 auto (pruned), 1 full K2 scan, 2 pruned
   int32_t last_rescored = 0;       // (query, range) pairs K2 re-scored in the last host search
-  int32_t last_eps_filters = 0;    // filters of the last cm_bm25_search_lists that took filtered_eps
+  int32_t last_eps_filters = 0;    // filters of the last cm_bm25_search_lists that took the epsilon floor
+  int32_t last_eps_passes = 0;     // postings passes of the last cm_bm25_filter_eps_multi / cm_bm25_search_lists
   int32_t nhead = 0;
   int64_t npad = 0;
   int32_t lut_dmin = 0;                  // first doc length of K2's ratio table window
@@ -1159,6 +1160,7 @@ struct cm_bm25 {
   int64_t head_max_bytes = 8ll << 30;    // tile memory budget
   std::vector<double> idf_host;
   DevBuf ws, qbuf, obuf, allow_buf, tmp;
+  DevBuf eps_ws;        // cm_bm25_eps.inc's own workspace (a list search's ws, tmp and allow_buf are live beside it)
   KernelTimer timer;    // K2 events (cm_bm25_timing)
   KernelTimer timer_b;  // K2b events (cm_bm25_timing_drain_block)
 };
@@ -1526,7 +1528,7 @@ int32_t count_rescored(cm_bm25 *h, int nq, const BmWs &w, hipStream_t st) {
 
 void bm25_free(cm_bm25 *h) {
   for (DevBuf *b : {&h->term_off, &h->post_doc, &h->post_tf, &h->post_pos, &h->dl, &h->live, &h->idf, &h->ws,
-                    &h->qbuf, &h->obuf, &h->allow_buf, &h->tmp, &h->headtf, &h->head_id, &h->head_maxtf,
+                    &h->qbuf, &h->obuf, &h->allow_buf, &h->tmp, &h->eps_ws, &h->headtf, &h->head_id, &h->head_maxtf,
                     &h->range_mindl, &h->blk_maxtf, &h->blk_mindl, &h->blk_maxr, &h->blk16_maxr})
     b->release();
 }
@@ -1771,6 +1773,7 @@ int bm25_finish_build(cm_bm25 *h, hipStream_t st) {
 #include "cm_bm25_append.inc"
 #include "cm_bm25_remove.inc"
 #include "cm_bm25_replace.inc"
+#include "cm_bm25_eps.inc"
 #include "cm_bm25_lists.inc"
 
 extern "C" {

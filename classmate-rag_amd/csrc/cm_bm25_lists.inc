@@ -13,7 +13,8 @@
 //   2. df     bm25_list_df_kernel: one workgroup per (filter-term, 256 rows of the filter's list);
 //             a thread looks its row up in the term (list_tf below), one atomic per wave.
 //   3. idf    L[Nc - df] - L[df] from the handle's log table (cm_bm25_prepare_filtered's: glibc
-//             logs, rank_bm25's bits); filters with a negative idf take filtered_eps.
+//             logs, rank_bm25's bits); the filters with a negative idf take their epsilon floors from
+//             one batched call, up to 32 of them a postings pass (cm_bm25_eps.inc).
 //   4. score  bm25_list_score_kernel: one workgroup per (query, 256 rows of its filter's list), one
 //             candidate per thread, the query's terms in query order with bm25_scatter_term_kernel's
 //             operands: bm25_search_full's sums, hence the fused path's.
@@ -257,6 +258,7 @@ int cm_bm25_search_lists(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_of
     CM_FAIL(CM_EUNSUPPORTED, "cm_bm25_search_lists: n_filters x ceil(ndocs / 32) must stay below 2^31: split the batch");
   const int32_t n_slots = q_off[nq];
   h->last_eps_filters = 0;
+  h->last_eps_passes = 0;
   int rc;
   // ---- 1. lists: count + length sums, scan, one read-back ----
   std::vector<int64_t> stat(2 * (size_t)n_filters + 1, 0);   // off[0 .. n_filters], then sum_len[0 .. n_filters)
@@ -410,14 +412,25 @@ int cm_bm25_search_lists(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_of
       std::vector<int32_t> neg((size_t)n_filters, 0);
       CM_HIP(hipMemcpyAsync(neg.data(), neg_dev, neg.size() * 4, hipMemcpyDeviceToHost, h->stream));
       CM_HIP(hipStreamSynchronize(h->stream));
+      std::vector<int64_t> e_off, e_nc, e_len;   // the filters with a negative idf: one batched call (cm_bm25_eps.inc)
+      std::vector<int32_t> e_f;
       for (int f = 0; f < n_filters; ++f) {
         if (!neg[f]) continue;
-        // (reads the filter's bitmap where it lies; writes obuf only)
-        if ((rc = filtered_eps(h, h->allow_buf.as<uint32_t>() + (int64_t)f * nw, off[f + 1] - off[f], &eps[f]))) return rc;
-        h->last_eps_filters += 1;
+        e_f.push_back(f);
+        e_off.push_back((int64_t)f * nw);
+        e_nc.push_back(off[f + 1] - off[f]);
+        e_len.push_back(sum_len[f]);
       }
-      if (h->last_eps_filters)
+      if (!e_f.empty()) {
+        // (reads the filters' bitmaps where they lie; writes eps_ws only)
+        std::vector<double> e_eps(e_f.size(), 0.0);
+        if ((rc = bm25_eps_multi(h, h->allow_buf.as<uint32_t>(), (int)e_f.size(), e_off.data(), e_nc.data(), e_len.data(),
+                                 e_eps.data())))
+          return rc;
+        for (size_t u = 0; u < e_f.size(); ++u) eps[e_f[u]] = e_eps[u];
+        h->last_eps_filters = (int32_t)e_f.size();
         CM_HIP(hipMemcpyAsync(eps_dev, eps.data(), eps.size() * 8, hipMemcpyHostToDevice, h->stream));
+      }
     }
     if (n_slots > 0) {
       hipLaunchKernelGGL(bm25_list_slots_kernel, dim3((unsigned)ceil_div(n_slots, 256)), dim3(256), 0, h->stream,

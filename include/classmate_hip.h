@@ -363,8 +363,9 @@ int cm_bm25_search(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_off, int
  * No scan and no posting walk: the allowed live rows of every bitmap are compacted into a row list,
  * and each (query, row) pair is scored outright, its tf looked up in the term's head tile or by a
  * binary search of its postings; one segmented sort orders every query's candidates (DESIGN §3
- * "BM25 row-list search").  Only a bitmap with a negative idf costs a pass over all postings (its
- * epsilon); cm_bm25_last_eps_filters = how many of the last call's did (-1: null handle).
+ * "BM25 row-list search").  Only the bitmaps with a negative idf need their epsilon, and up to 32 of
+ * them share one pass over all postings (cm_bm25_filter_eps_multi's);
+ * cm_bm25_last_eps_filters = how many of the last call's did (-1: null handle).
  * A null handle or argument, nq < 1, k < 1, n_filters < 1, a filter_of entry outside [0, n_filters)
  * and a decreasing q_off -> CM_EINVAL, checked on the host before any device call; 2^31 or more
  * (query, allowed row) pairs, or n_filters x ceil(ndocs/32) words -> CM_EUNSUPPORTED; a bitmap some
@@ -430,6 +431,21 @@ int cm_bm25_filter_stats_dev(cm_bm25 *h, const uint32_t *allow_dev, const int32_
 int cm_bm25_filter_term_stats_dev(cm_bm25 *h, const uint32_t *allow_dev, int64_t *df_dev, uint64_t *first_dev,
                                   void *stream);
 int cm_bm25_filter_eps(cm_bm25 *h, const uint32_t *allow_bits, double *eps_out);
+/* cm_bm25_filter_eps for n_filters bitmaps at once: eps_out[f] (host, n_filters doubles) is bit for
+ * bit what cm_bm25_filter_eps returns for bitmap f (0.0 for a bitmap without candidates).
+ * allow_bits: n_filters bitmaps of ceil(ndocs/32) words each, one after the other, host or device
+ * memory.  Up to 32 bitmaps share one pass over the postings (a 32-bit membership word per
+ * document); the candidate vocabulary, its first-occurrence order, the idfs and the sequential
+ * fp64 sum stay on the device, and one (sum, count) pair per bitmap is read back (DESIGN §3 "BM25
+ * epsilon floors, 32 clauses a pass").  Host function: runs on the handle's stream, synchronises.
+ * A null argument or n_filters < 0 -> CM_EINVAL; n_filters == 0 -> CM_OK, nothing done; n_filters x
+ * ceil(ndocs/32) >= 2^31 - 1 words -> CM_EUNSUPPORTED (all checked before any device call); a bitmap
+ * whose candidates hold no tokens -> CM_EZERODIV (cm_bm25_filter_eps' message); a failed workspace
+ * allocation -> CM_ENOMEM.  The handle stays usable after every error. */
+int cm_bm25_filter_eps_multi(cm_bm25 *h, const uint32_t *allow_bits, int32_t n_filters, double *eps_out);
+/* Postings passes (rounds of up to 32 bitmaps) taken by the last cm_bm25_filter_eps_multi or
+ * cm_bm25_search_lists call on the handle; -1 for a null handle. */
+int32_t cm_bm25_last_eps_passes(cm_bm25 *h);
 int cm_bm25_search_stats_dev(cm_bm25 *h, const int32_t *q_terms_dev, const int32_t *q_off_dev, int32_t nq,
                              int32_t total_terms, int32_t k, const uint32_t *allow_dev, const int64_t *stats_dev,
                              const int64_t *df_dev, const double *eps_dev, double *score_dev, int64_t *row_dev,
