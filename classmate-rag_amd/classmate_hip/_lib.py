@@ -70,6 +70,7 @@ SIGNATURES = {
     "cm_dense_dim": (c_i32, c_vp),
     "cm_dense_search": (c_int, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp),
     "cm_dense_search_lists": (c_int, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp),
+    "cm_dense_search_lists_dev": (c_int, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp),
     "cm_dense_search_workspace": (c_i64, c_vp, c_i32, c_i32),
     "cm_dense_search_kind": (c_i32, c_vp, c_i32, c_i32),
     "cm_dense_set_path": (c_int, c_vp, c_i32),
@@ -112,6 +113,8 @@ SIGNATURES = {
     "cm_bm25_set_stats": (c_int, c_vp, c_vp, c_i32, c_i64, c_i64, c_f64),
     "cm_bm25_search": (c_int, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp),
     "cm_bm25_search_lists": (c_int, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp),
+    "cm_bm25_search_lists_dev": (c_int, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                 c_vp),
     "cm_bm25_last_eps_filters": (c_i32, c_vp),
     "cm_bm25_workspace_items": (c_i64, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64),
     "cm_bm25_workspace_subblocks": (c_i64, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64),

@@ -73,10 +73,11 @@ class _StreamOwner:
             pass
 
 
-def _list_allow_words(allow_words, need: int):
+def _list_allow_words(allow_words, need: int, sync: bool = True):
     """search_lists' bitmaps as one (n_filters, need) array of words, host (numpy uint32) or device
     (a contiguous tensor): from a numpy array, a device tensor, or a sequence of ``where_bits``
-    outputs (host words or device tensors)."""
+    outputs (host words or device tensors).  ``sync=False``: the caller's C function waits for
+    torch's current stream itself (the _dev forms)."""
     if isinstance(allow_words, (list, tuple)):
         if not allow_words:
             raise ValueError("allow_words holds no bitmap")
@@ -98,7 +99,8 @@ def _list_allow_words(allow_words, need: int):
         ab = np.zeros((ab.shape[0], 1), np.uint32)
     if hasattr(ab, "data_ptr"):     # rows of exactly `need` words
         ab = ab.contiguous()
-        torch.cuda.current_stream(ab.device).synchronize()   # the copy above runs on torch's stream
+        if sync:
+            torch.cuda.current_stream(ab.device).synchronize()   # the copy above runs on torch's stream
     else:
         ab = _c(ab, np.uint32)
     return ab
@@ -219,12 +221,34 @@ class DenseIndex:
                                         L.ptr(vecs)), "cm_dense_search")
         return (dist, rows, vecs) if return_vectors else (dist, rows)
 
-    def search_lists(self, q: np.ndarray, k: int, allow_words, filter_of, return_vectors: bool = False):
+    def search_lists(self, q, k: int, allow_words, filter_of, return_vectors: bool = False, *, dev: bool = False):
         """``search`` for a batch whose queries carry different where clauses (cm_dense_search_lists:
         no scan, the allowed live rows of each clause are gathered from a row list; exact fp64
         distances).  allow_words: (n_filters, words) bitmaps -- a numpy array, a device tensor, or a
         sequence of ``where_bits`` outputs (host words or device tensors); filter_of: (nq,) the
-        bitmap of each query.  Same outputs as ``search``."""
+        bitmap of each query.  Same outputs as ``search``.  ``dev=True`` (cm_dense_search_lists_dev):
+        q is a (nq, dim) float32 device tensor, consumed in the order of torch's current stream; the
+        result is (dist, rows) as device tensors with the same bits, complete on return."""
+        if dev:
+            if return_vectors:
+                raise ValueError("the device form returns no vectors: gather_dev(rows)")
+            if q.dim() != 2 or q.shape[1] != self.dim or q.dtype != torch.float32:
+                raise ValueError(f"q must be (nq, {self.dim}) float32, got {tuple(q.shape)} {q.dtype}")
+            qq = q.contiguous()
+            nq = qq.shape[0]
+            ab = _list_allow_words(allow_words, (self.size + 31) // 32, sync=False)
+            fo = _c(np.asarray(filter_of), np.int32)
+            if fo.shape != (nq,):
+                raise ValueError(f"filter_of has shape {fo.shape}, need ({nq},)")
+            if nq and (fo.min() < 0 or fo.max() >= ab.shape[0]):
+                raise ValueError(f"filter_of entries must be in [0, {ab.shape[0]})")
+            dist = torch.empty((nq, k), dtype=torch.float32, device=qq.device)
+            rows = torch.empty((nq, k), dtype=torch.int64, device=qq.device)
+            if nq:
+                L.check(L.fn["cm_dense_search_lists_dev"](self._h, L.ptr(qq), nq, int(k), L.ptr(ab), int(ab.shape[0]),
+                                                          L.ptr(fo), L.ptr(dist), L.ptr(rows), _stream(self.device)),
+                        "cm_dense_search_lists_dev")
+            return dist, rows
         qq = _c(np.atleast_2d(q), np.float32)
         if qq.shape[1] != self.dim:
             raise ValueError(f"query dim {qq.shape[1]} != index dim {self.dim}")
@@ -582,24 +606,48 @@ class BM25Index:
                                        L.ptr(rows), L.ptr(nvalid)), "cm_bm25_search")
         return scores, rows, nvalid
 
-    def search_lists(self, queries: Sequence[Sequence[int]], k: int, allow_words, filter_of):
+    def search_lists(self, queries: Sequence[Sequence[int]], k: int, allow_words, filter_of, *, dev: bool = False,
+                     eps_io: Optional[np.ndarray] = None):
         """``search`` for a batch whose queries carry different where clauses (cm_bm25_search_lists:
         the allowed live rows of each clause are scored from a row list, with the clause's own
         statistics; bit for bit what ``search([q], k, allow_words[filter_of[i]])`` returns per
         query, for any k >= 1).  allow_words and filter_of as ``DenseIndex.search_lists``.  Same
-        outputs as ``search``."""
+        outputs as ``search``.  ``dev=True`` (cm_bm25_search_lists_dev): scores and rows come back as
+        device tensors (same bits, complete on return; the bitmaps are consumed in the order of
+        torch's current stream), nvalid as numpy.  ``eps_io`` (device form only): a C-contiguous
+        float64 array of one epsilon floor per bitmap, NaN = not known; known floors are used, the
+        ones this call had to compute are written into it (see ``last_eps_filters``)."""
+        if eps_io is not None:
+            if not dev:
+                raise ValueError("eps_io needs dev=True")
+            if (not isinstance(eps_io, np.ndarray) or eps_io.dtype != np.float64 or eps_io.ndim != 1
+                    or not eps_io.flags.c_contiguous or not eps_io.flags.writeable):
+                raise ValueError("eps_io must be a writeable C-contiguous 1-d float64 array")
         nq = len(queries)
         off = np.zeros(nq + 1, np.int32)
         for i, q in enumerate(queries):
             off[i + 1] = off[i] + len(q)
         flat = np.concatenate([np.asarray(q, np.int32) for q in queries]) if off[-1] else np.zeros(1, np.int32)
         flat = _c(flat, np.int32)
-        ab = _list_allow_words(allow_words, (self.num_docs + 31) // 32)
+        ab = _list_allow_words(allow_words, (self.num_docs + 31) // 32, sync=not dev)
         fo = _c(np.asarray(filter_of), np.int32)
         if fo.shape != (nq,):
             raise ValueError(f"filter_of has shape {fo.shape}, need ({nq},)")
         if nq and (fo.min() < 0 or fo.max() >= ab.shape[0]):
             raise ValueError(f"filter_of entries must be in [0, {ab.shape[0]})")
+        if dev:
+            if eps_io is not None and eps_io.shape[0] != ab.shape[0]:
+                raise ValueError(f"eps_io has {eps_io.shape[0]} entries for {ab.shape[0]} bitmaps")
+            tdev = torch.device("cuda", self.device)
+            scores = torch.empty((nq, k), dtype=torch.float64, device=tdev)
+            rows = torch.empty((nq, k), dtype=torch.int64, device=tdev)
+            nvalid = np.empty(nq, np.int32)
+            if nq:
+                L.check(L.fn["cm_bm25_search_lists_dev"](self._h, L.ptr(flat), L.ptr(off), nq, int(k), L.ptr(ab),
+                                                         int(ab.shape[0]), L.ptr(fo), L.ptr(eps_io), L.ptr(scores),
+                                                         L.ptr(rows), L.ptr(nvalid), _stream(self.device)),
+                        "cm_bm25_search_lists_dev")
+            return scores, rows, nvalid
         scores = np.empty((nq, k), np.float64)
         rows = np.empty((nq, k), np.int64)
         nvalid = np.empty(nq, np.int32)

@@ -670,38 +670,58 @@ class BM25Store:
         selective ones (vector_store.route_clauses under BM25's constants) share row-list searches
         (engine.BM25Index.search_lists, each clause with its own statistics: quirk Q2), the others --
         and every clause of a negative top_k or of a sharded index -- run _search_one_clause."""
-        from .vector_store import group_clauses, route_clauses
-        group_of, clauses = group_clauses(where)
         out: List[List[Dict[str, Any]]] = [[] for _ in queries]
+        plan = self._plan_clauses(queries, where, top_k)
 
-        bits = None
-
-        def per_clause(g, sel):
-            res = self._search_one_clause([queries[i] for i in sel], clauses[g] if g >= 0 else None, top_k,
-                                          bits[g] if bits and g >= 0 else None)
+        def per_clause(sel, clause, bits):
+            res = self._search_one_clause([queries[i] for i in sel], clause, top_k, bits)
             for i, r in zip(sel, res):
                 out[i] = r
 
-        groups = sorted(set(group_of))
-        if groups and groups[0] < 0:
-            per_clause(-1, [i for i, x in enumerate(group_of) if x < 0])
+        if plan["plain"]:
+            per_clause(plan["plain"], None, None)
+        for sel, clause, bits, _ in plan["scan"]:
+            per_clause(sel, clause, bits)
+        for sel, k, words, filter_of, _ in plan["lists"]:
+            qids = [self._query_ids(queries[i]) for i in sel]
+            scores, rows, nvalid = self._index.search_lists(qids, k, words, filter_of)
+            for j, i in enumerate(sel):
+                out[i] = [self._hit(s, r) for s, r in zip(scores[j][: nvalid[j]], rows[j][: nvalid[j]])]
+        return out
+
+    def _plan_clauses(self, queries: Sequence[str], where, top_k: int):
+        """The searches that answer a batch with one where clause per query -- what _search_clauses
+        runs with host arrays and device_batch.retrieve_batch_clauses with device tensors, so both
+        route alike.  Every distinct clause is evaluated once (group_clauses, where_bits) and routed
+        by vector_store.route_clauses under this module's constants and $CM_BM25_LIST_CUTOFF_DIV.
+        Returns {"plain": queries without a clause (one unfiltered search), "scan": [(queries,
+        clause, where_bits output or None, k)] one filtered search each -- k = min(top_k, Nc), None
+        when the clause was not evaluated here (no list route: a negative top_k, a sharded index) --
+        and "lists": [(non-blank queries, k, [allow words per bitmap], filter_of, [clause per
+        bitmap])], one search_lists call each with k = min(top_k, the largest clause of the call), calls without a non-blank query
+        or with k <= 0 left out}.  A query whose clause allows no row is in none of them; plain and
+        scan keep their blank queries (_search_one_clause drops them).  Builds the index."""
+        from .vector_store import group_clauses, route_clauses
+        group_of, clauses = group_clauses(where)
+        plan = {"plain": [i for i, g in enumerate(group_of) if g < 0], "scan": [], "lists": []}
         if not clauses or not self._entries:
-            return out
+            return plan
         self._ensure_index()
         idx = self._index
         has_lists = hasattr(idx, "search_lists") and top_k >= 0
+        bits = None
         if has_lists:
             self._ensure_meta()
             bits = [engine.where_bits(self._meta, w, "bm25", idx.device) for w in clauses]   # once per distinct clause
         # (without the list route the plan only groups: _search_one_clause evaluates its own clause)
         counts = [n for _, n in bits] if bits else [1] * len(clauses)
         forced = os.environ.get("CM_BM25_LIST_CUTOFF_DIV")
-        plan = route_clauses(group_of, counts, len(self._id_list), max(top_k, 0), 1 << 62, has_lists,
-                             float(forced or BM25_LIST_CUTOFF_DIV), BM25_LIST_PAIR_BUDGET,
-                             0.0 if forced else BM25_LIST_PAIR_DIV)   # forced: rows alone
-        for g, sel in plan["scan"]:
-            per_clause(g, sel)
-        for call in plan["lists"]:
+        routed = route_clauses(group_of, counts, len(self._id_list), max(top_k, 0), 1 << 62, has_lists,
+                               float(forced or BM25_LIST_CUTOFF_DIV), BM25_LIST_PAIR_BUDGET,
+                               0.0 if forced else BM25_LIST_PAIR_DIV)   # forced: rows alone
+        for g, sel in routed["scan"]:
+            plan["scan"].append((sel, clauses[g], bits[g] if bits else None, min(top_k, counts[g]) if bits else None))
+        for call in routed["lists"]:
             sel = [i for _, qs in call for i in qs if queries[i].strip()]   # blank queries give []
             if not sel:
                 continue
@@ -710,11 +730,8 @@ class BM25Store:
             k = min(top_k, max(counts[g] for g, _ in call))   # per clause min(top_k, Nc): nvalid
             if k <= 0:
                 continue
-            qids = [self._query_ids(queries[i]) for i in sel]
-            scores, rows, nvalid = idx.search_lists(qids, k, [bits[g][0] for g, _ in call], filter_of)
-            for j, i in enumerate(sel):
-                out[i] = [self._hit(s, r) for s, r in zip(scores[j][: nvalid[j]], rows[j][: nvalid[j]])]
-        return out
+            plan["lists"].append((sel, k, [bits[g][0] for g, _ in call], filter_of, [clauses[g] for g, _ in call]))
+        return plan
 
     def _hit(self, score, row) -> Dict[str, Any]:
         e = self._entries[self._id_list[int(row)]]

@@ -11,6 +11,9 @@ search (K1c/K1s), pool gather + MMR (K4), BM25 top-k (K2a/K2b/K2 + K3; with a fi
 statistics over the allowed candidates, quirk Q2), pool preparation + RRF merge (K5).  This module
 chains them without a host round trip and builds result dicts only for the final top_k items of
 each query.  Single questions are a batch of one (their E5 encode replays a small-batch graph).
+A batch with one filter per question takes the same chain (``retrieve_batch_clauses``): the stores
+plan the searches as their host routes do, the selective clauses share the row-list searches in
+their device form, and pools shorter than the MMR pool are served.
 
 Id matching: the merge compares integer keys.  A document's key is its vector-store row; a BM25
 document that the vector store does not hold gets ``n_vector_rows + bm25_row``.  The BM25-row ->
@@ -59,13 +62,18 @@ def applicable(retr, filters, hybrid: bool) -> bool:
     """The device path covers hybrid retrieval with MMR over this package's stores, filtered or not
     (anything else takes the host path).  With a filter, ``retrieve_batch`` may still decline
     (None) when fewer vectors than the MMR pool pass it: the host path's k clamp covers that."""
+    if not hybrid or not retr.use_mmr:
+        return False
+    if isinstance(filters, (list, tuple)):   # one filter per question: applicable_clauses
+        return False
+    return _stores_applicable(retr)
+
+
+def _stores_applicable(retr) -> bool:
+    """``applicable``'s conditions on the stores and the retriever's sizes."""
     from .bm25 import BM25Store
     from .vector_store import GpuVectorStore
     vs, bm = retr.vector_store, retr.bm25_store
-    if not hybrid or not retr.use_mmr:
-        return False
-    if isinstance(filters, (list, tuple)):   # one filter per question: the host path groups them
-        return False
     if not isinstance(vs, GpuVectorStore) or not isinstance(bm, BM25Store):
         return False
     vs._ensure_loaded()
@@ -78,6 +86,21 @@ def applicable(retr, filters, hybrid: bool) -> bool:
     # the host path clamps k to the candidates; the device path needs full lists
     # live rows = the store's id -> row map (a device popcount + sync per call before)
     return len(vs._row) >= pool and len(bm._id_list) >= retr.k_bm25
+
+
+def applicable_clauses(retr, filters, hybrid: bool) -> bool:
+    """``applicable`` for one filter per question (a list or tuple): the same conditions, and both
+    indexes must offer ``search_lists`` -- the sharded ones do not and keep the host path.  A clause
+    that allows fewer vectors than the MMR pool is served (short pools), never declined.  Every cell
+    of the measurement (DESIGN §3 "Hybrid batches with per-question clauses") is at least as fast as
+    the host path, so there is no further routing rule here."""
+    if not hybrid or not retr.use_mmr or not isinstance(filters, (list, tuple)):
+        return False
+    if not _stores_applicable(retr):
+        return False
+    bm = retr.bm25_store
+    bm._ensure_index()
+    return hasattr(retr.vector_store._index, "search_lists") and hasattr(bm._index, "search_lists")
 
 
 def _query_vectors(embedder, questions: Sequence[str], dev):
@@ -175,6 +198,27 @@ def _bm25_filtered(bm, q_terms, q_off, k: int, allow, where, cache: dict):
     return s, r
 
 
+def _keymap(vs, bm, device: int) -> _KeyMap:
+    key = (vs._uid, vs._version, bm._uid, bm._version)   # the stores themselves (never-reused uids)
+    km = _KEYMAPS.get(key)
+    if km is None:
+        km = _KeyMap(vs, bm, device)
+        if len(_KEYMAPS) >= _KEYMAPS_MAX:
+            _KEYMAPS.clear()
+        _KEYMAPS[key] = km
+    return km
+
+
+def _side_stream(dev, main):
+    import torch
+    if os.environ.get("CLASSMATE_BM25_SAME_STREAM") == "1":     # A/B: the serial schedule
+        return main
+    side = _SIDE_STREAMS.get(dev)
+    if side is None:
+        side = _SIDE_STREAMS[dev] = torch.cuda.Stream(device=dev)
+    return side
+
+
 def retrieve_batch(retr, questions: Sequence[str], top_k: int,
                    filters: Optional[Dict[str, Any]] = None) -> Optional[List[List[Dict[str, Any]]]]:
     """retr.retrieve_batch(questions, filters, top_k, hybrid=True) on the device (see module
@@ -200,23 +244,12 @@ def retrieve_batch(retr, questions: Sequence[str], top_k: int,
         bm._ensure_meta()
         allow_b, n_cand = _allow(bm._meta, filters, "bm25", index.device, (len(bm._id_list) + 31) // 32, cache)
         kb = min(kb, n_cand)
-    key = (vs._uid, vs._version, bm._uid, bm._version)   # the stores themselves (never-reused uids)
-    km = _KEYMAPS.get(key)
-    if km is None:
-        km = _KeyMap(vs, bm, index.device)
-        if len(_KEYMAPS) >= _KEYMAPS_MAX:
-            _KEYMAPS.clear()
-        _KEYMAPS[key] = km
+    km = _keymap(vs, bm, index.device)
     # BM25 runs on a side stream that waits only for the allow bitmaps / key map above, so it
     # overlaps the encode and the dense search (a filtered search's status read then waits for the
     # BM25 kernels alone, not for the dense scan queued ahead of it)
     main = torch.cuda.current_stream(dev)
-    if os.environ.get("CLASSMATE_BM25_SAME_STREAM") == "1":     # A/B: the serial schedule
-        side = main
-    else:
-        side = _SIDE_STREAMS.get(dev)
-        if side is None:
-            side = _SIDE_STREAMS[dev] = torch.cuda.Stream(device=dev)
+    side = _side_stream(dev, main)
     ready = torch.cuda.Event()
     ready.record(main)
     # E5 encode first (its launches return at once), so the host tokenizes the BM25 queries while
@@ -256,8 +289,19 @@ def retrieve_batch(retr, questions: Sequence[str], top_k: int,
     # between here and the host copies below cannot recycle their blocks under main's kernels
     for t in (bs, br, bkeys, q_terms, q_off):
         t.record_stream(main)
+    return _merge_and_build(retr, km, r, d, order, bkeys, bs, top_k, kv + kb)
+
+
+def _merge_and_build(retr, km, r, d, order, bkeys, bs, top_k: int, n_items: int) -> List[List[Dict[str, Any]]]:
+    """The tail both chains share: pool preparation + RRF merge (K5) on torch's current stream, one
+    device-to-host copy, result dicts of the final items.  r, d: the (nq, pool) rows and distances
+    (row -1 = no entry); order: K4's MMR order; bkeys, bs: the BM25 lists as merge keys and scores
+    (key -1 = no entry); n_items: an upper bound of the items of one question (k for top_k <= 0)."""
+    import torch
+    vs, bm = retr.vector_store, retr.bm25_store
+    nq = r.shape[0]
     vk, vd, vn, bn = engine.rrf_pool_prep_dev(r.contiguous(), d.contiguous(), order, bkeys.contiguous())
-    k_dev = top_k if top_k > 0 else kv + kb
+    k_dev = top_k if top_k > 0 else n_items
     ok, of, ov, ob, ofl, on = engine.rrf_merge_dev(vk, vd, vn, bkeys.contiguous(), bs.contiguous(), bn,
                                                    w_vec=retr.weight_vector, w_bm25=retr.weight_bm25,
                                                    rrf_k=retr.rrf_k, top_k=k_dev)
@@ -313,3 +357,145 @@ def retrieve_batch(retr, questions: Sequence[str], top_k: int,
                                    "fused": ofi[j]}})
         out.append(res)
     return out
+
+
+# Epsilon floors of a batch with per-question clauses, one float per (BM25 version, clause), keyed
+# like _bm25_filtered's: the largest single cost of either BM25 route depends on the clause and the
+# index only.  The row-list calls take and return them through eps_io, the per-clause filtered
+# searches through _bm25_filtered's cache argument.  _ALLOW_CACHE's rule (cleared when full) with a
+# bound of its own: an entry here is one float, not a bitmap of the corpus, and a batch may carry
+# hundreds of distinct clauses.
+_EPS_CACHE: dict = {}
+_EPS_CACHE_MAX = 4096
+
+
+def _eps_key(bm, clause):
+    """_bm25_filtered's key of a clause's floor (None: the clause has no stable form, not cached)."""
+    fk = _filter_key(bm._meta, clause, "bm25")
+    return None if fk is None else ("eps", bm._uid, bm._version) + fk
+
+
+def _eps_store(key, eps: float) -> None:
+    if len(_EPS_CACHE) >= _EPS_CACHE_MAX:
+        _EPS_CACHE.clear()
+    _EPS_CACHE[key] = eps
+
+
+def _dev_words(words, n_words: int, dev):
+    """A where_bits bitmap (host words or a device tensor) as a device tensor of >= n_words words."""
+    import torch
+    if not hasattr(words, "data_ptr"):
+        words = torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).to(dev)
+    if words.numel() < n_words:             # rows past the metadata (never written): not allowed
+        words = torch.cat([words, torch.zeros(n_words - words.numel(), dtype=words.dtype, device=words.device)])
+    return words
+
+
+def _rows_index(sel, dev):
+    import torch
+    return torch.from_numpy(np.asarray(sel, np.int64)).pin_memory().to(dev, non_blocking=True)
+
+
+def retrieve_batch_clauses(retr, questions: Sequence[str], top_k: int, filters) -> List[List[Dict[str, Any]]]:
+    """retr.retrieve_batch(questions, filters=[one per question], top_k, hybrid=True) on the device;
+    the caller checked ``applicable_clauses`` and the length of ``filters``.  Both stores plan the
+    batch exactly as their host routes do (GpuVectorStore._plan_clauses, BM25Store._plan_clauses:
+    one evaluation per distinct clause, scans for the unselective ones, row-list searches for the
+    others), every search lands in one (nq, pool) / (nq, k_bm25) pair of device tensors padded with
+    row -1, and the rest is ``retrieve_batch``'s: gather + K4 with the pools' own lengths, BM25 on
+    the side stream, K5, result dicts for the final items only."""
+    import torch
+    from .filters import build_where_filter
+    vs, bm = retr.vector_store, retr.bm25_store
+    index, bindex = vs._index, bm._index
+    dev = torch.device("cuda", index.device)
+    nq = len(questions)
+    kv, kb = retr.k_vector, retr.k_bm25
+    pool = max(kv, retr.mmr_max_pool)
+    chroma_where = [build_where_filter(f) if f else None for f in filters]
+    vplan = vs._plan_clauses(chroma_where, pool)
+    bplan = bm._plan_clauses(questions, [f or None for f in filters], kb)   # (blank questions count, as on the host)
+    bindex = bm._index
+    km = _keymap(vs, bm, index.device)
+    nwv, nwb = (index.size + 31) // 32, (len(bm._id_list) + 31) // 32
+    main = torch.cuda.current_stream(dev)
+    side = _side_stream(dev, main)
+    ready = torch.cuda.Event()
+    ready.record(main)              # the bitmaps and the key map
+    # ---- dense, asynchronous part: encode, the unfiltered search, one scan per unselective clause ----
+    q = _query_vectors(retr.embedder, questions, dev)
+    d = torch.zeros((nq, pool), dtype=torch.float32, device=dev)
+    r = torch.full((nq, pool), -1, dtype=torch.int64, device=dev)
+
+    def put(dst, sel, parts):
+        at = _rows_index(sel, dst[0].device)
+        for t, p in zip(dst, parts):
+            t[at, :p.shape[1]] = p
+
+    if vplan["plain"]:
+        # (applicable: at least `pool` live rows, so the host path's k clamp leaves pool)
+        sel = vplan["plain"]
+        put((d, r), sel, index.search_dev(q.index_select(0, _rows_index(sel, dev)), pool))
+    for sel, k, allow in vplan["scan"]:
+        # defer_exact=False: the deferred form parks its state in the index's one workspace
+        put((d, r), sel, index.search_dev(q.index_select(0, _rows_index(sel, dev)), k,
+                                          allow=_dev_words(allow, nwv, dev)))
+    # ---- BM25 on the side stream; its list calls block the host while the dense work above runs ----
+    blank = [not q_.strip() for q_ in questions]
+    with torch.cuda.stream(side):
+        side.wait_event(ready)
+        bs = torch.zeros((nq, kb), dtype=torch.float64, device=dev)
+        br = torch.full((nq, kb), -1, dtype=torch.int64, device=dev)
+        keep = [bs, br]
+
+        def terms(sel):
+            qids = [bm._query_ids(questions[i]) for i in sel]
+            off = np.zeros(len(sel) + 1, np.int32)
+            off[1:] = np.cumsum([len(x) for x in qids])
+            flat = np.asarray([t for x in qids for t in x] or [0], np.int32)
+            qt = torch.from_numpy(flat).pin_memory().to(dev, non_blocking=True)
+            qo = torch.from_numpy(off).pin_memory().to(dev, non_blocking=True)
+            keep.extend((qt, qo))
+            return qids, qt, qo
+
+        sel = [i for i in bplan["plain"] if not blank[i]]
+        if sel:
+            _, qt, qo = terms(sel)
+            put((bs, br), sel, bindex.search_dev(qt, qo, kb))
+        for sel, clause, bits, k in bplan["scan"]:
+            sel = [i for i in sel if not blank[i]]
+            if not sel or k <= 0:
+                continue
+            _, qt, qo = terms(sel)
+            # _bm25_filtered keeps a floor as a device tensor under the key it forms itself: hand it
+            # this clause's entry of _EPS_CACHE alone, and take a floor it had to compute back
+            key = _eps_key(bm, clause)
+            known = _EPS_CACHE.get(key) if key is not None else None
+            one = {} if known is None else {key: torch.tensor([known], dtype=torch.float64, device=dev)}
+            put((bs, br), sel, _bm25_filtered(bm, qt, qo, k, _dev_words(bits[0], nwb, dev), clause, one))
+            if known is None and key in one:
+                _eps_store(key, float(one[key].item()))
+        for sel, k, words, filter_of, clauses in bplan["lists"]:
+            qids = [bm._query_ids(questions[i]) for i in sel]
+            keys = [_eps_key(bm, c) for c in clauses]
+            eps = np.array([_EPS_CACHE.get(key, np.nan) if key is not None else np.nan for key in keys], np.float64)
+            known = ~np.isnan(eps)
+            s_, r_, _ = bindex.search_lists(qids, k, words, filter_of, dev=True, eps_io=eps)
+            for key, e, was in zip(keys, eps.tolist(), known.tolist()):
+                if key is not None and not was and e == e:      # computed by this call
+                    _eps_store(key, e)
+            keep.extend((s_, r_))
+            put((bs, br), sel, (s_, r_))
+        bkeys = torch.where(br >= 0, km.bm2key_dev[br.clamp(min=0)], torch.full_like(br, -1))
+        keep.append(bkeys)
+    # ---- dense, blocking part: the row-list searches (consume q in main's order) ----
+    for sel, k, words, filter_of in vplan["lists"]:
+        put((d, r), sel, index.search_lists(q.index_select(0, _rows_index(sel, dev)), k, words, filter_of, dev=True))
+    # ---- finish: join, K4 over the pools' own lengths, K5 ----
+    main.wait_stream(side)
+    for t in keep:
+        t.record_stream(main)
+    n_valid = (r >= 0).sum(dim=1).to(torch.int32)
+    vecs = index.gather_dev(r.reshape(-1)).view(nq, pool, index.dim)     # row -1: zeros
+    order = engine.mmr_dev(q, vecs, kv, float(retr.mmr_lambda), n_valid=n_valid)
+    return _merge_and_build(retr, km, r, d, order, bkeys, bs, top_k, kv + kb)

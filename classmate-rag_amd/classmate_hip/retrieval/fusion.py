@@ -6,8 +6,9 @@ values; the arithmetic runs in HIP kernels (K4 MMR, K5 RRF merge) instead of
 Python/numpy.  ``HybridRetriever.retrieve_batch`` is the batched form: one
 embedder call, one dense search, one MMR launch, one BM25 launch and one RRF
 launch for the whole batch (per-query semantics unchanged).  Hybrid MMR
-queries -- single or batched, filtered or not -- stay on the device end to end
-(``device_batch``; CM_RETRIEVE_DEVICE=0 takes the host path).
+queries -- single or batched, filtered or not, one filter for the batch or one
+per question -- stay on the device end to end (``device_batch``;
+CM_RETRIEVE_DEVICE=0 takes the host path).
 """
 from __future__ import annotations
 
@@ -214,10 +215,14 @@ class HybridRetriever:
         if not questions:
             return []
         if isinstance(filters, (list, tuple)):
-            # one filter dict per question: the host path, build_where_filter per question (the stores
-            # group equal clauses); result i equals retrieve(question=questions[i], filters=filters[i])
+            # one filter dict per question; result i equals retrieve(question=questions[i],
+            # filters=filters[i]).  The device chain when it applies, else the host path:
+            # build_where_filter per question, and the stores group equal clauses
             if len(filters) != len(questions):
                 raise ValueError(f"filters holds {len(filters)} entries for {len(questions)} questions")
+            if (os.environ.get("CM_RETRIEVE_DEVICE", "1") != "0"
+                    and device_batch.applicable_clauses(self, filters, hybrid)):
+                return device_batch.retrieve_batch_clauses(self, questions, top_k, filters)
             chroma_where = [build_where_filter(f) if f else None for f in filters]
             bm_where = [f or None for f in filters]
             if not (hasattr(self.vector_store, "query_batch") and hasattr(self.bm25_store, "search_batch")):

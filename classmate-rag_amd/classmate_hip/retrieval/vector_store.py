@@ -655,13 +655,7 @@ class GpuVectorStore:
         if self._index is None:
             return out
         idx = self._index
-        group_of, clauses = group_clauses(wheres)
-        bits = [engine.where_bits(self._meta, w, "chroma", idx.device) for w in clauses]   # once per distinct clause
-        counts = [n for _, n in bits]
-        plan = route_clauses(group_of, counts, len(self._ids), top_k, engine.L.max_topk(),
-                             hasattr(idx, "search_lists"), _list_cutoff_div(), LIST_PAIR_BUDGET,
-                             0.0 if os.environ.get("CM_LIST_CUTOFF_DIV") else LIST_PAIR_DIV)   # forced: rows alone
-        need = (idx.size + 31) // 32
+        plan = self._plan_clauses(wheres, top_k)
 
         def fill(sel, res):
             vecs = res[2] if include_embeddings else None
@@ -674,15 +668,40 @@ class GpuVectorStore:
             res = self._search(q[plan["plain"]], None, top_k, include_embeddings)
             if res is not None:
                 fill(plan["plain"], res)
-        for g, sel in plan["scan"]:
-            fill(sel, idx.search(q[sel], min(top_k, counts[g]), bits[g][0], return_vectors=include_embeddings))
-        for call in plan["lists"]:
+        for sel, k, allow in plan["scan"]:
+            fill(sel, idx.search(q[sel], k, allow, return_vectors=include_embeddings))
+        for sel, k, words, filter_of in plan["lists"]:
+            fill(sel, idx.search_lists(q[sel], k, words, filter_of, return_vectors=include_embeddings))
+        return out
+
+    def _plan_clauses(self, wheres, top_k: int):
+        """The searches that answer a batch with one where clause per query -- what
+        _query_batch_clauses runs with host arrays and device_batch.retrieve_batch_clauses with
+        device tensors, so both route alike (the list route's distances are the fp64 formula's, the
+        scans' the certified re-rank's: another route, other last bits).  Every distinct clause is
+        evaluated once (group_clauses, where_bits) and routed by route_clauses under this module's
+        constants and $CM_LIST_CUTOFF_DIV.  Returns {"plain": queries without a clause (one ordinary
+        search), "scan": [(queries, k, allow words)] one filtered search each with k = min(top_k,
+        the clause's rows), "lists": [(queries, k, [allow words per bitmap], filter_of)] one
+        search_lists call each with k = min(top_k, the largest clause of the call)}; a query whose
+        clause allows no row is in none of them.  The index must exist."""
+        idx = self._index
+        group_of, clauses = group_clauses(wheres)
+        bits = [engine.where_bits(self._meta, w, "chroma", idx.device) for w in clauses]   # once per distinct clause
+        counts = [n for _, n in bits]
+        routed = route_clauses(group_of, counts, len(self._ids), top_k, engine.L.max_topk(),
+                               hasattr(idx, "search_lists"), _list_cutoff_div(), LIST_PAIR_BUDGET,
+                               0.0 if os.environ.get("CM_LIST_CUTOFF_DIV") else LIST_PAIR_DIV)   # forced: rows alone
+        need = (idx.size + 31) // 32
+        lists = []
+        for call in routed["lists"]:
             sel = [i for _, qs in call for i in qs]
             filter_of = np.concatenate([np.full(len(qs), f, np.int32) for f, (_, qs) in enumerate(call)])
             k = min(top_k, max(counts[g] for g, _ in call))
-            fill(sel, idx.search_lists(q[sel], k, [self._fit_words(bits[g][0], need) for g, _ in call], filter_of,
-                                       return_vectors=include_embeddings))
-        return out
+            lists.append((sel, k, [self._fit_words(bits[g][0], need) for g, _ in call], filter_of))
+        return {"plain": routed["plain"],
+                "scan": [(sel, min(top_k, counts[g]), bits[g][0]) for g, sel in routed["scan"]],
+                "lists": lists}
 
     @_locked
     def query_batch(self, *, query_embeddings: np.ndarray, where=None, top_k: int = 8,

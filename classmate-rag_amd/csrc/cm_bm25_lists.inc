@@ -22,6 +22,9 @@
 //             segments, whose input is in ascending row order; the first min(k, Nc) of each segment.
 // Quirk Q2 is why the statistics are per filter; quirk Q1 (zero scores pad in row order) is the
 // stable sort's.  No posting crosses to the host.
+// cm_bm25_search_lists_dev is the same body with the results on the device (the top-k kernel writes
+// the caller's tensors; the handle's stream first waits for the caller's) and with eps_io: epsilon
+// floors the caller knows already take no postings pass, computed ones are handed back.
 
 namespace cm {
 
@@ -231,23 +234,25 @@ __global__ void __launch_bounds__(256) bm25_list_topk_kernel(const uint64_t *__r
   }
 }
 
-}  // namespace cm
-
-extern "C" {
-
-int cm_bm25_search_lists(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_off, int32_t nq, int32_t k,
-                         const uint32_t *allow_bits, int32_t n_filters, const int32_t *filter_of, double *out_score,
-                         int64_t *out_row, int32_t *out_n) {
+// cm_bm25_search_lists and cm_bm25_search_lists_dev: one body.  on_dev: out_score and out_row are
+// device memory, and `stream` (the caller's) is waited for before the handle's stream starts.
+// eps_io (nullable, host, n_filters doubles): the epsilon floors the caller knows, NaN = not known;
+// a known one is used as it is, a computed one is written back.
+static int bm25_search_lists_impl(const char *fn, bool on_dev, cm_bm25 *h, const int32_t *q_terms, const int32_t *q_off,
+                                  int32_t nq, int32_t k, const uint32_t *allow_bits, int32_t n_filters,
+                                  const int32_t *filter_of, double *eps_io, double *out_score, int64_t *out_row,
+                                  int32_t *out_n, hipStream_t stream) {
+  const std::string F(fn);
   // ---- argument checks: host only, before any device call ----
   if (!h) CM_FAIL(CM_EINVAL, "null handle");
-  if (nq < 1) CM_FAIL(CM_EINVAL, "cm_bm25_search_lists: nq must be >= 1");
-  if (k < 1) CM_FAIL(CM_EINVAL, "cm_bm25_search_lists: k must be >= 1");
-  if (n_filters < 1) CM_FAIL(CM_EINVAL, "cm_bm25_search_lists: n_filters must be >= 1");
+  if (nq < 1) CM_FAIL(CM_EINVAL, F + ": nq must be >= 1");
+  if (k < 1) CM_FAIL(CM_EINVAL, F + ": k must be >= 1");
+  if (n_filters < 1) CM_FAIL(CM_EINVAL, F + ": n_filters must be >= 1");
   if (!q_terms || !q_off || !allow_bits || !filter_of || !out_score || !out_row || !out_n)
     CM_FAIL(CM_EINVAL, "NULL argument");
   for (int i = 0; i < nq; ++i)
     if (filter_of[i] < 0 || filter_of[i] >= n_filters)
-      CM_FAIL(CM_EINVAL, "cm_bm25_search_lists: filter_of[" + std::to_string(i) + "] = " +
+      CM_FAIL(CM_EINVAL, F + ": filter_of[" + std::to_string(i) + "] = " +
                              std::to_string(filter_of[i]) + " is outside [0, n_filters)");
   if (q_off[0] < 0) CM_FAIL(CM_EINVAL, "bad q_off");
   for (int i = 0; i < nq; ++i)
@@ -255,11 +260,12 @@ int cm_bm25_search_lists(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_of
   DeviceGuard dg(h->dev);
   const int64_t ndocs = h->ndocs, nw = ceil_div(ndocs, 32), total = (int64_t)n_filters * nw;
   if (total + 1 > INT32_MAX)
-    CM_FAIL(CM_EUNSUPPORTED, "cm_bm25_search_lists: n_filters x ceil(ndocs / 32) must stay below 2^31: split the batch");
+    CM_FAIL(CM_EUNSUPPORTED, F + ": n_filters x ceil(ndocs / 32) must stay below 2^31: split the batch");
   const int32_t n_slots = q_off[nq];
   h->last_eps_filters = 0;
   h->last_eps_passes = 0;
   int rc;
+  if (on_dev && (rc = stream_wait_stream(h->stream, stream))) return rc;   // the producer of allow_bits
   // ---- 1. lists: count + length sums, scan, one read-back ----
   std::vector<int64_t> stat(2 * (size_t)n_filters + 1, 0);   // off[0 .. n_filters], then sum_len[0 .. n_filters)
   int64_t *prefix = nullptr, *off_dev = nullptr;
@@ -303,7 +309,7 @@ int cm_bm25_search_lists(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_of
       CM_FAIL(CM_EZERODIV, "float division by zero (candidate documents have no tokens)");
     n_keys += nc;
     if (n_keys > INT32_MAX)
-      CM_FAIL(CM_EUNSUPPORTED, "cm_bm25_search_lists: more than 2^31 (query, row) pairs: split the batch");
+      CM_FAIL(CM_EUNSUPPORTED, F + ": more than 2^31 (query, row) pairs: split the batch");
     seg[i + 1] = (int32_t)n_keys;
     used[f] = 1;
     out_n[i] = (int32_t)std::min<int64_t>(k, nc);
@@ -339,7 +345,7 @@ int cm_bm25_search_lists(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_of
       sc_items.push_back(BmListItem{i, (int32_t)c});
   }
   if (df_items.size() > (size_t)INT32_MAX || n_ft > INT32_MAX)
-    CM_FAIL(CM_EUNSUPPORTED, "cm_bm25_search_lists: too many work items: split the batch");
+    CM_FAIL(CM_EUNSUPPORTED, F + ": too many work items: split the batch");
   std::vector<double> avgdl((size_t)n_filters, 1.0);   // (Nc == 0: nothing is scored)
   for (int f = 0; f < n_filters; ++f)
     if (off[f + 1] > off[f]) avgdl[f] = (double)sum_len[f] / (double)(off[f + 1] - off[f]);
@@ -379,8 +385,9 @@ int cm_bm25_search_lists(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_of
   int32_t *seg_dev = reinterpret_cast<int32_t *>(at(seg_o));
   uint64_t *keys = reinterpret_cast<uint64_t *>(at(keys_o)), *skeys = reinterpret_cast<uint64_t *>(at(skeys_o));
   int32_t *vals = reinterpret_cast<int32_t *>(at(vals_o)), *svals = reinterpret_cast<int32_t *>(at(svals_o));
-  double *d_score = reinterpret_cast<double *>(at(osc_o));
-  int64_t *d_row = reinterpret_cast<int64_t *>(at(orow_o));
+  // (device form: the top-k kernel writes the caller's tensors)
+  double *d_score = on_dev ? out_score : reinterpret_cast<double *>(at(osc_o));
+  int64_t *d_row = on_dev ? out_row : reinterpret_cast<int64_t *>(at(orow_o));
   const int32_t *head_id = h->nhead ? h->head_id.as<int32_t>() : (const int32_t *)nullptr;
   std::vector<double> eps((size_t)n_filters, 0.0);   // (host sources of async copies: alive until the last synchronise)
   CM_HIP(hipMemcpyAsync(seg_dev, seg.data(), seg.size() * 4, hipMemcpyHostToDevice, h->stream));
@@ -414,8 +421,14 @@ int cm_bm25_search_lists(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_of
       CM_HIP(hipStreamSynchronize(h->stream));
       std::vector<int64_t> e_off, e_nc, e_len;   // the filters with a negative idf: one batched call (cm_bm25_eps.inc)
       std::vector<int32_t> e_f;
+      bool any_neg = false;
       for (int f = 0; f < n_filters; ++f) {
         if (!neg[f]) continue;
+        any_neg = true;
+        if (eps_io && !std::isnan(eps_io[f])) {   // the caller's floor: no postings pass for this filter
+          eps[f] = eps_io[f];
+          continue;
+        }
         e_f.push_back(f);
         e_off.push_back((int64_t)f * nw);
         e_nc.push_back(off[f + 1] - off[f]);
@@ -427,10 +440,13 @@ int cm_bm25_search_lists(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_of
         if ((rc = bm25_eps_multi(h, h->allow_buf.as<uint32_t>(), (int)e_f.size(), e_off.data(), e_nc.data(), e_len.data(),
                                  e_eps.data())))
           return rc;
-        for (size_t u = 0; u < e_f.size(); ++u) eps[e_f[u]] = e_eps[u];
+        for (size_t u = 0; u < e_f.size(); ++u) {
+          eps[e_f[u]] = e_eps[u];
+          if (eps_io) eps_io[e_f[u]] = e_eps[u];
+        }
         h->last_eps_filters = (int32_t)e_f.size();
-        CM_HIP(hipMemcpyAsync(eps_dev, eps.data(), eps.size() * 8, hipMemcpyHostToDevice, h->stream));
       }
+      if (any_neg) CM_HIP(hipMemcpyAsync(eps_dev, eps.data(), eps.size() * 8, hipMemcpyHostToDevice, h->stream));
     }
     if (n_slots > 0) {
       hipLaunchKernelGGL(bm25_list_slots_kernel, dim3((unsigned)ceil_div(n_slots, 256)), dim3(256), 0, h->stream,
@@ -452,11 +468,31 @@ int cm_bm25_search_lists(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_of
   hipLaunchKernelGGL(bm25_list_topk_kernel, dim3((unsigned)ceil_div((int64_t)nq * k, 256)), dim3(256), 0, h->stream, skeys,
                      svals, seg_dev, nq, k, d_score, d_row);
   CM_HIP(hipGetLastError());
-  CM_HIP(hipMemcpyAsync(out_score, d_score, (size_t)nq * k * 8, hipMemcpyDeviceToHost, h->stream));
-  CM_HIP(hipMemcpyAsync(out_row, d_row, (size_t)nq * k * 8, hipMemcpyDeviceToHost, h->stream));
-  CM_HIP(hipStreamSynchronize(h->stream));
+  if (!on_dev) {
+    CM_HIP(hipMemcpyAsync(out_score, d_score, (size_t)nq * k * 8, hipMemcpyDeviceToHost, h->stream));
+    CM_HIP(hipMemcpyAsync(out_row, d_row, (size_t)nq * k * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  CM_HIP(hipStreamSynchronize(h->stream));   // the host sources above, and the outputs: complete on return
   h->last_rescored = -1;
   return CM_OK;
+}
+
+}  // namespace cm
+
+extern "C" {
+
+int cm_bm25_search_lists(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_off, int32_t nq, int32_t k,
+                         const uint32_t *allow_bits, int32_t n_filters, const int32_t *filter_of, double *out_score,
+                         int64_t *out_row, int32_t *out_n) {
+  return bm25_search_lists_impl("cm_bm25_search_lists", false, h, q_terms, q_off, nq, k, allow_bits, n_filters,
+                                filter_of, nullptr, out_score, out_row, out_n, nullptr);
+}
+
+int cm_bm25_search_lists_dev(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_off, int32_t nq, int32_t k,
+                             const uint32_t *allow_bits, int32_t n_filters, const int32_t *filter_of, double *eps_io,
+                             double *score_dev, int64_t *row_dev, int32_t *out_n, void *stream) {
+  return bm25_search_lists_impl("cm_bm25_search_lists_dev", true, h, q_terms, q_off, nq, k, allow_bits, n_filters,
+                                filter_of, eps_io, score_dev, row_dev, out_n, static_cast<hipStream_t>(stream));
 }
 
 int32_t cm_bm25_last_eps_filters(cm_bm25 *h) { return h ? h->last_eps_filters : -1; }

@@ -167,6 +167,18 @@ __device__ inline void f16x3_split2(float a, float b, uint32_t &hi, uint32_t &lo
   lo = __builtin_bit_cast(uint32_t, l);
 }
 
+// `own` waits (on the device, not the host) for everything enqueued on `producer` so far.
+inline int stream_wait_stream(hipStream_t own, hipStream_t producer) {
+  if (own == producer) return CM_OK;
+  hipEvent_t ev;
+  CM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  hipError_t e = hipEventRecord(ev, producer);
+  if (e == hipSuccess) e = hipStreamWaitEvent(own, ev, 0);
+  (void)hipEventDestroy(ev);   // (released once the recorded work completes)
+  CM_HIP(e);
+  return CM_OK;
+}
+
 constexpr uint64_t kEmptyKey = ~0ull;
 constexpr int kMaxTopK = 256;
 

@@ -16,6 +16,9 @@
 //             every segment: ascending (distance, row), pads (0.f, -1) past the segment's end, the
 //             finish of dense_search_full.
 // No scan, seed, re-rank or plane is touched; only C and the live bitmap are read.
+// cm_dense_search_lists_dev is the same body with the queries and the results on the device: the
+// padded queries and their fp64 norms come from list_query_prep_kernel instead of the host loop, the
+// top-k kernel writes the caller's tensors, and the handle's stream first waits for the caller's.
 
 namespace cm {
 
@@ -200,29 +203,66 @@ __global__ void __launch_bounds__(256) list_topk_kernel(const uint64_t *__restri
 
 }  // namespace cm
 
-extern "C" {
+namespace cm {
 
-int cm_dense_search_lists(cm_dense *h, const float *q, int32_t nq, int32_t k, const uint32_t *allow_bits,
-                          int32_t n_filters, const int32_t *filter_of, float *out_dist, int64_t *out_row,
-                          float *out_vec) {
+// Padded queries and their fp64 norms from device queries (cm_dense_search_lists_dev): one workgroup
+// per query.  qp[i][0 .. ld) = q[i][0 .. dim) then zeros; qnorm[i] = sqrt of the host loop's sum --
+// s += (double)v * v over the dims in order, ONE sequential chain (a tree gives other bits), the
+// products exact in fp64.  The block stages kListNormChunk dims at a time in LDS with coalesced
+// loads, thread 0 adds them in order.
+constexpr int kListNormChunk = 2048;
+
+__global__ void __launch_bounds__(256) list_query_prep_kernel(const float *__restrict__ q, int dim, int ld,
+                                                              float *__restrict__ qp, double *__restrict__ qnorm) {
+  __shared__ float s_v[kListNormChunk];
+  const float *src = q + (int64_t)blockIdx.x * dim;
+  float *dst = qp + (int64_t)blockIdx.x * ld;
+  double s = 0.0;
+  for (int c0 = 0; c0 < ld; c0 += kListNormChunk) {
+    const int n = min(kListNormChunk, ld - c0);
+    __syncthreads();
+    for (int c = threadIdx.x; c < n; c += 256) {
+      const float v = c0 + c < dim ? src[c0 + c] : 0.f;
+      s_v[c] = v;
+      dst[c0 + c] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int m = min(n, dim - c0);   // the pads add nothing: left out, as on the host
+      for (int c = 0; c < m; ++c) {
+        const double v = (double)s_v[c];
+        s += v * v;
+      }
+    }
+  }
+  if (threadIdx.x == 0) qnorm[blockIdx.x] = __dsqrt_rn(s);
+}
+
+// cm_dense_search_lists and cm_dense_search_lists_dev: one body.  on_dev: q, out_dist and out_row
+// are device memory, and `stream` (the caller's) is waited for before the handle's stream starts.
+static int dense_search_lists_impl(const char *fn, bool on_dev, cm_dense *h, const float *q, int32_t nq, int32_t k,
+                                   const uint32_t *allow_bits, int32_t n_filters, const int32_t *filter_of,
+                                   float *out_dist, int64_t *out_row, float *out_vec, hipStream_t stream) {
+  const std::string F(fn);
   // ---- argument checks: host only, before any device call ----
   if (!h) CM_FAIL(CM_EINVAL, "null handle");
-  if (nq < 1) CM_FAIL(CM_EINVAL, "cm_dense_search_lists: nq must be >= 1");
-  if (k < 1) CM_FAIL(CM_EINVAL, "cm_dense_search_lists: k must be >= 1");
-  if (n_filters < 1) CM_FAIL(CM_EINVAL, "cm_dense_search_lists: n_filters must be >= 1");
+  if (nq < 1) CM_FAIL(CM_EINVAL, F + ": nq must be >= 1");
+  if (k < 1) CM_FAIL(CM_EINVAL, F + ": k must be >= 1");
+  if (n_filters < 1) CM_FAIL(CM_EINVAL, F + ": n_filters must be >= 1");
   if (!q || !allow_bits || !filter_of || !out_dist || !out_row) CM_FAIL(CM_EINVAL, "NULL argument");
   for (int i = 0; i < nq; ++i)
     if (filter_of[i] < 0 || filter_of[i] >= n_filters)
-      CM_FAIL(CM_EINVAL, "cm_dense_search_lists: filter_of[" + std::to_string(i) + "] = " +
+      CM_FAIL(CM_EINVAL, F + ": filter_of[" + std::to_string(i) + "] = " +
                              std::to_string(filter_of[i]) + " is outside [0, n_filters)");
   if (k > kMaxTopK)
-    CM_FAIL(CM_EUNSUPPORTED, "cm_dense_search_lists: k above cm_max_topk(): use cm_dense_search per clause");
+    CM_FAIL(CM_EUNSUPPORTED, F + ": k above cm_max_topk(): use cm_dense_search per clause");
   DeviceGuard dg(h->dev);
   const int64_t size = h->size, nw = ceil_div(size, 32), total = (int64_t)n_filters * nw;
   const int ld = h->ld, dim = h->dim;
   if (total + 1 > INT32_MAX)
-    CM_FAIL(CM_EUNSUPPORTED, "cm_dense_search_lists: n_filters x ceil(size / 32) must stay below 2^31: split the batch");
+    CM_FAIL(CM_EUNSUPPORTED, F + ": n_filters x ceil(size / 32) must stay below 2^31: split the batch");
   int rc;
+  if (on_dev && (rc = stream_wait_stream(h->stream, stream))) return rc;   // the producers of q and allow_bits
   // ---- 1. list lengths: count, scan, read back ----
   std::vector<int64_t> off((size_t)n_filters + 1, 0);
   int64_t *prefix = nullptr, *off_dev = nullptr;
@@ -256,7 +296,7 @@ int cm_dense_search_lists(cm_dense *h, const float *q, int32_t nq, int32_t k, co
   for (int i = 0; i < nq; ++i) {
     n_keys += off[filter_of[i] + 1] - off[filter_of[i]];
     if (n_keys > INT32_MAX)
-      CM_FAIL(CM_EUNSUPPORTED, "cm_dense_search_lists: more than 2^31 (query, row) pairs: split the batch");
+      CM_FAIL(CM_EUNSUPPORTED, F + ": more than 2^31 (query, row) pairs: split the batch");
     seg[i + 1] = (int32_t)n_keys;
     qstart[filter_of[i] + 1] += 1;
   }
@@ -276,7 +316,7 @@ int cm_dense_search_lists(cm_dense *h, const float *q, int32_t nq, int32_t k, co
         items.push_back(ListItem{f, (int32_t)c, qstart[f] + t, std::min(qt, nqf - t)});
   }
   if (items.size() > (size_t)INT32_MAX)
-    CM_FAIL(CM_EUNSUPPORTED, "cm_dense_search_lists: too many work items: split the batch");
+    CM_FAIL(CM_EUNSUPPORTED, F + ": too many work items: split the batch");
   // ---- workspace ----
   size_t sort_b = 0;
   if (n_keys > 0)
@@ -295,7 +335,7 @@ int cm_dense_search_lists(cm_dense *h, const float *q, int32_t nq, int32_t k, co
   const size_t obytes = (size_t)nq * k * (4 + 8);
   const size_t vbytes = out_vec ? (size_t)nq * k * dim * 4 : 0;
   if ((rc = h->ws.ensure(o))) return rc;
-  if ((rc = h->out_buf.ensure(round_up(obytes, 256) + vbytes))) return rc;
+  if (!on_dev && (rc = h->out_buf.ensure(round_up(obytes, 256) + vbytes))) return rc;
   char *base = h->ws.as<char>();
   uint32_t *rows = reinterpret_cast<uint32_t *>(base + rows_o);
   ListItem *items_dev = reinterpret_cast<ListItem *>(base + items_o);
@@ -303,26 +343,32 @@ int cm_dense_search_lists(cm_dense *h, const float *q, int32_t nq, int32_t k, co
   float *qp = reinterpret_cast<float *>(base + qp_o);
   double *qn_dev = reinterpret_cast<double *>(base + qn_o);
   uint64_t *keys = reinterpret_cast<uint64_t *>(base + keys_o), *sorted = reinterpret_cast<uint64_t *>(base + sorted_o);
-  float *d_dist = h->out_buf.as<float>();
-  int64_t *d_row = reinterpret_cast<int64_t *>(h->out_buf.as<char>() + round_up((int64_t)nq * k * 4, 8));
+  // (device form: the top-k kernel writes the caller's tensors)
+  float *d_dist = on_dev ? out_dist : h->out_buf.as<float>();
+  int64_t *d_row = on_dev ? out_row : reinterpret_cast<int64_t *>(h->out_buf.as<char>() + round_up((int64_t)nq * k * 4, 8));
   CM_HIP(hipMemcpyAsync(seg_dev, seg.data(), seg.size() * 4, hipMemcpyHostToDevice, h->stream));
   std::vector<float> qpad;   // host sources of the copies below: alive until the last synchronise
   std::vector<double> qn;
   if (n_keys > 0) {
     // queries padded to ld, and their norms in fp64: dense_search_full's
-    qpad.assign((size_t)nq * ld, 0.f);
-    qn.resize((size_t)nq);
-    for (int i = 0; i < nq; ++i) {
-      double s = 0.0;
-      for (int c = 0; c < dim; ++c) {
-        const float v = q[(int64_t)i * dim + c];
-        qpad[(size_t)i * ld + c] = v;
-        s += (double)v * v;
+    if (on_dev) {
+      hipLaunchKernelGGL(list_query_prep_kernel, dim3((unsigned)nq), dim3(256), 0, h->stream, q, dim, ld, qp, qn_dev);
+      CM_HIP(hipGetLastError());
+    } else {
+      qpad.assign((size_t)nq * ld, 0.f);
+      qn.resize((size_t)nq);
+      for (int i = 0; i < nq; ++i) {
+        double s = 0.0;
+        for (int c = 0; c < dim; ++c) {
+          const float v = q[(int64_t)i * dim + c];
+          qpad[(size_t)i * ld + c] = v;
+          s += (double)v * v;
+        }
+        qn[i] = std::sqrt(s);
       }
-      qn[i] = std::sqrt(s);
+      CM_HIP(hipMemcpyAsync(qp, qpad.data(), qpad.size() * 4, hipMemcpyHostToDevice, h->stream));
+      CM_HIP(hipMemcpyAsync(qn_dev, qn.data(), qn.size() * 8, hipMemcpyHostToDevice, h->stream));
     }
-    CM_HIP(hipMemcpyAsync(qp, qpad.data(), qpad.size() * 4, hipMemcpyHostToDevice, h->stream));
-    CM_HIP(hipMemcpyAsync(qn_dev, qn.data(), qn.size() * 8, hipMemcpyHostToDevice, h->stream));
     CM_HIP(hipMemcpyAsync(qord_dev, qorder.data(), qorder.size() * 4, hipMemcpyHostToDevice, h->stream));
     CM_HIP(hipMemcpyAsync(items_dev, items.data(), items.size() * 16, hipMemcpyHostToDevice, h->stream));
     // ---- 1b. the lists ----
@@ -347,11 +393,31 @@ int cm_dense_search_lists(cm_dense *h, const float *q, int32_t nq, int32_t k, co
     d_vec = reinterpret_cast<float *>(h->out_buf.as<char>() + round_up(obytes, 256));
     if ((rc = cm_dense_gather_dev(h, d_row, (int64_t)nq * k, d_vec, h->stream))) return rc;
   }
-  CM_HIP(hipMemcpyAsync(out_dist, d_dist, (size_t)nq * k * 4, hipMemcpyDeviceToHost, h->stream));
-  CM_HIP(hipMemcpyAsync(out_row, d_row, (size_t)nq * k * 8, hipMemcpyDeviceToHost, h->stream));
-  if (out_vec) CM_HIP(hipMemcpyAsync(out_vec, d_vec, vbytes, hipMemcpyDeviceToHost, h->stream));
-  CM_HIP(hipStreamSynchronize(h->stream));
+  if (!on_dev) {
+    CM_HIP(hipMemcpyAsync(out_dist, d_dist, (size_t)nq * k * 4, hipMemcpyDeviceToHost, h->stream));
+    CM_HIP(hipMemcpyAsync(out_row, d_row, (size_t)nq * k * 8, hipMemcpyDeviceToHost, h->stream));
+    if (out_vec) CM_HIP(hipMemcpyAsync(out_vec, d_vec, vbytes, hipMemcpyDeviceToHost, h->stream));
+  }
+  CM_HIP(hipStreamSynchronize(h->stream));   // the host sources above, and the outputs: complete on return
   return CM_OK;
+}
+
+}  // namespace cm
+
+extern "C" {
+
+int cm_dense_search_lists(cm_dense *h, const float *q, int32_t nq, int32_t k, const uint32_t *allow_bits,
+                          int32_t n_filters, const int32_t *filter_of, float *out_dist, int64_t *out_row,
+                          float *out_vec) {
+  return dense_search_lists_impl("cm_dense_search_lists", false, h, q, nq, k, allow_bits, n_filters, filter_of, out_dist,
+                                 out_row, out_vec, nullptr);
+}
+
+int cm_dense_search_lists_dev(cm_dense *h, const float *q_dev, int32_t nq, int32_t k, const uint32_t *allow_bits,
+                              int32_t n_filters, const int32_t *filter_of, float *dist_dev, int64_t *row_dev,
+                              void *stream) {
+  return dense_search_lists_impl("cm_dense_search_lists_dev", true, h, q_dev, nq, k, allow_bits, n_filters, filter_of,
+                                 dist_dev, row_dev, nullptr, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

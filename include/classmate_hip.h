@@ -137,6 +137,21 @@ int cm_dense_search(cm_dense *h, const float *q, int32_t nq, int32_t k, const ui
 int cm_dense_search_lists(cm_dense *h, const float *q, int32_t nq, int32_t k, const uint32_t *allow_bits,
                           int32_t n_filters, const int32_t *filter_of, float *out_dist, int64_t *out_row,
                           float *out_vec);
+/* cm_dense_search_lists (ChromaVectorStore.query, rag/retrieval/vector_chroma.py:204-253, per-query
+ * where clauses) with the queries and the results on the device: q_dev (nq x dim fp32), dist_dev and
+ * row_dev (nq x k) are device memory; allow_bits host or device memory and filter_of host memory, as
+ * above.  There is no out_vec: the caller gathers rows itself (cm_dense_gather_dev).  The same body as
+ * cm_dense_search_lists and the same bits: the queries are padded and their fp64 norms summed by a
+ * device kernel in the host loop's order (one sequential fp64 chain per query, a correctly rounded
+ * square root).  Stream contract: the work runs on the handle's own stream behind an event recorded
+ * on `stream` (the caller's: a producer of q_dev or allow_bits enqueued on it before the call is
+ * waited for on the device); the list lengths are read back as in the host function, so the call
+ * synchronises the handle's stream -- never the device -- and the outputs are complete when it
+ * returns.  Not graph-capturable.  Argument checks and return codes as cm_dense_search_lists, on the
+ * host before any device call. */
+int cm_dense_search_lists_dev(cm_dense *h, const float *q_dev, int32_t nq, int32_t k, const uint32_t *allow_bits,
+                              int32_t n_filters, const int32_t *filter_of, float *dist_dev, int64_t *row_dev,
+                              void *stream);
 /* workspace bytes cm_dense_search_dev needs for (nq, k). */
 int64_t cm_dense_search_workspace(cm_dense *h, int32_t nq, int32_t k);
 /* which scan kernel cm_dense_search[_dev] runs for (nq, k): CM_DENSE_F32
@@ -374,6 +389,23 @@ int cm_bm25_search(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_off, int
 int cm_bm25_search_lists(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_off, int32_t nq, int32_t k,
                          const uint32_t *allow_bits, int32_t n_filters, const int32_t *filter_of,
                          double *out_score, int64_t *out_row, int32_t *out_n);
+/* cm_bm25_search_lists (BM25Store.search, rag/retrieval/bm25.py:175-212, per-query where clauses)
+ * with the results on the device: score_dev and row_dev (nq x k) are device memory; q_terms, q_off,
+ * filter_of and out_n stay on the host (tokenising is host work; out_n is known after the first
+ * read-back), allow_bits host or device memory.  The same body and the same bits.
+ * eps_io (nullable, host, n_filters doubles): the epsilon floors the caller already knows.  NaN on
+ * entry = not known (0.0 is a legitimate floor).  A bitmap that turns out to have a negative idf uses
+ * its eps_io value when it has one and joins no postings pass; with NaN its floor is computed as in
+ * the host function and written back.  A bitmap without a negative idf in this call is left
+ * untouched.  cm_bm25_last_eps_filters / cm_bm25_last_eps_passes count only what was computed.
+ * Stream contract: the work runs on the handle's own stream behind an event recorded on `stream`
+ * (the caller's: a producer of allow_bits enqueued on it before the call is waited for on the
+ * device); the call keeps the host function's read-backs, so it synchronises the handle's stream --
+ * never the device -- and the outputs are complete when it returns.  Not graph-capturable.
+ * Argument checks and return codes as cm_bm25_search_lists, on the host before any device call. */
+int cm_bm25_search_lists_dev(cm_bm25 *h, const int32_t *q_terms, const int32_t *q_off, int32_t nq, int32_t k,
+                             const uint32_t *allow_bits, int32_t n_filters, const int32_t *filter_of, double *eps_io,
+                             double *score_dev, int64_t *row_dev, int32_t *out_n, void *stream);
 int32_t cm_bm25_last_eps_filters(cm_bm25 *h);
 /* cm_bm25_search with the caller's statistics instead of this index's: q_idf[total] = every
  * query term's idf (0 for terms outside the candidate vocabulary; ignored for ids outside
