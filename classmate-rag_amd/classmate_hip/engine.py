@@ -300,6 +300,11 @@ class DenseIndex:
         finished from the complete candidate buffers (no exact scan) in the last host search()."""
         return int(L.fn["cm_dense_last_wide_reranks"](self._h))
 
+    def last_band_rows(self) -> int:
+        """Rows the K1q/K1q-s re-rank re-scored exactly (fp64, from the fp32 rows) in the last host
+        search(), summed over its queries: the certified band plus the pilot bound's rows."""
+        return int(L.fn["cm_dense_last_band_rows"](self._h))
+
     def timing(self, enable: bool = True):
         """Record HIP events around every search's scan kernel (see timing_drain)."""
         L.check(L.fn["cm_dense_timing"](self._h, int(bool(enable))), "cm_dense_timing")
@@ -326,6 +331,10 @@ class DenseIndex:
     def workspace_wide_reranks(self, nq: int, k: int, workspace) -> int:
         """last_wide_reranks for the device search that last used ``workspace`` (synchronous read)."""
         return int(L.fn["cm_dense_workspace_wide_reranks"](self._h, int(nq), int(k), L.ptr(workspace)))
+
+    def workspace_band_rows(self, nq: int, k: int, workspace) -> int:
+        """last_band_rows for the device search that last used ``workspace`` (synchronous read)."""
+        return int(L.fn["cm_dense_workspace_band_rows"](self._h, int(nq), int(k), L.ptr(workspace)))
 
     def workspace_bytes(self, nq: int, k: int) -> int:
         n = int(L.fn["cm_dense_search_workspace"](self._h, int(nq), int(k)))

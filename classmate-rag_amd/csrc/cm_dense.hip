@@ -1205,6 +1205,7 @@ struct cm_dense {
   int path = 0;                            // cm_dense_set_path (0 = automatic)
   int32_t last_fallbacks = -1;             // K1c queries re-run exactly by the last host search
   int32_t last_wide = -1;                  // K1q queries finished by the wide re-rank in the last host search
+  int64_t last_band = -1;                  // K1q rows the re-rank's fp64 stage re-scored in the last host search
   KernelTimer timer;                       // scan-kernel events (cm_dense_timing)
   hipEvent_t seed_event = nullptr;         // cm_dense_set_seed_event: recorded after K1q's seed pass
   uint32_t *live = nullptr;
@@ -1662,7 +1663,8 @@ struct CoarseWs {
   int32_t *fb_mask;   // queries sent to the exact K1 pass (K1q: 2 = the wide re-rank first)
   int32_t *fb_count;
   uint32_t *fb_bound; // K1q: kth_up of a query sent to the wide re-rank
-  int32_t *wide_ctr;  // K1q wide re-rank: [0] unused (once the slot allocator), [1] queries it finished
+  int32_t *wide_ctr;  // K1q wide re-rank: [0] unused (once the slot allocator), [1] queries it finished;
+                      // [2..3] one 64-bit count: rows the re-rank's fp64 stage re-scored (band_rows)
   uint32_t *wide_rows;   // [kWideSlots][kWideCap]
   uint64_t *wide_keys;   // [kWideSlots][kWideCap]
   DenseWs k1;         // the exact K1 pass's own workspace (used only for fb_mask queries)
@@ -1694,7 +1696,7 @@ CoarseWs coarse_ws_layout(const cm_dense *h, const CoarseCfg &c, int nq, int k, 
   w.fb_count = reinterpret_cast<int32_t *>(take(4));
   if (c.q8) {
     w.fb_bound = reinterpret_cast<uint32_t *>(take(nq_pad * 4));
-    w.wide_ctr = reinterpret_cast<int32_t *>(take(8));
+    w.wide_ctr = reinterpret_cast<int32_t *>(take(16));
     w.wide_rows = reinterpret_cast<uint32_t *>(take((int64_t)kWideSlots * kWideCap * 4));
     w.wide_keys = reinterpret_cast<uint64_t *>(take((int64_t)kWideSlots * kWideCap * 8));
   }
@@ -1779,7 +1781,7 @@ int launch_coarse(cm_dense *h, const float *q_dev, int nq, int k, int kind, cons
   CM_HIP(hipGetLastError());
   CM_HIP(hipMemsetAsync(w.fb_count, 0, 4, st));
   if (c.q8) {
-    CM_HIP(hipMemsetAsync(w.wide_ctr, 0, 8, st));
+    CM_HIP(hipMemsetAsync(w.wide_ctr, 0, 16, st));
     hipLaunchKernelGGL(dense_prep_q8, dim3(c.n_pass * c.qs), dim3(256), 0, st, q_dev, nq, h->dim, h->ld, w.qq, w.qsc,
                        reinterpret_cast<const uint32_t *>(h->rnorm));
     CM_HIP(hipGetLastError());
@@ -1827,9 +1829,11 @@ int launch_coarse(cm_dense *h, const float *q_dev, int nq, int k, int kind, cons
   CM_HIP(hipGetLastError());
   // 5. certificate + exact re-rank (failures -> fb_mask)
   if (c.q8) {
+    const bool pilot = env_knob("CM_K1Q_PILOT", true);   // 0: the int8 band from kth_up alone (A/B)
     hipLaunchKernelGGL(dense_rerank_q8_kernel, dim3(nq), dim3(kQRT), kQRerankLds, st, w.keys, w.ups, w.cnt, c.n_wg,
                        c.qs, k, nq, h->C, h->ld, h->dim, q_dev, w.qsc, xh_full(h) ? h->Xh : nullptr, w.qh, w.qnorm,
-                       h->rnorm, dist_dev, row_dev, w.fb_mask, w.fb_count, w.fb_bound);
+                       h->rnorm, dist_dev, row_dev, w.fb_mask, w.fb_count, w.fb_bound,
+                       pilot ? 1 : 0, reinterpret_cast<unsigned long long *>(w.wide_ctr + 2));
     CM_HIP(hipGetLastError());
     // band overflow with complete candidate buffers: the wide re-rank (gated; ~5 us when none failed;
     // CM_K1Q_WIDE=0: the exact scan takes every failing query, A/B)
@@ -1928,6 +1932,7 @@ int dense_search_full(cm_dense *h, const float *q, int nq, int k, const uint32_t
   }
   h->last_fallbacks = 0;
   h->last_wide = 0;
+  h->last_band = 0;
   return CM_OK;
 }
 
@@ -2165,6 +2170,19 @@ int32_t cm_dense_workspace_wide_reranks(cm_dense *h, int32_t nq, int32_t k, cons
 
 int32_t cm_dense_last_wide_reranks(cm_dense *h) { return h ? h->last_wide : -1; }
 
+int64_t cm_dense_workspace_band_rows(cm_dense *h, int32_t nq, int32_t k, const void *workspace_dev) {
+  if (!h || !workspace_dev || nq <= 0 || k <= 0 || k > kMaxTopK) return -1;
+  const int kind = dense_kind(h, nq, k);
+  if (kind != CM_DENSE_Q8 && kind != CM_DENSE_Q8S) return 0;
+  DeviceGuard dg(h->dev);
+  const CoarseWs w = coarse_ws_layout(h, coarse_config(h, nq, kind), nq, k, const_cast<void *>(workspace_dev));
+  int64_t c = -1;
+  if (hipMemcpy(&c, w.wide_ctr + 2, 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  return c;
+}
+
+int64_t cm_dense_last_band_rows(cm_dense *h) { return h ? h->last_band : -1; }
+
 int cm_dense_set_seed_event(cm_dense *h, void *event) {
   if (!h) CM_FAIL(CM_EINVAL, "null handle");
   h->seed_event = (hipEvent_t)event;
@@ -2321,11 +2339,15 @@ int cm_dense_search(cm_dense *h, const float *q, int32_t nq, int32_t k, const ui
   if (out_vec) CM_HIP(hipMemcpyAsync(out_vec, d_vec, vbytes, hipMemcpyDeviceToHost, h->stream));
   h->last_fallbacks = 0;
   h->last_wide = 0;
+  h->last_band = 0;
   const int kind = dense_kind(h, nq, k);
   if (kind != CM_DENSE_F32) {
     const CoarseWs w = coarse_ws_layout(h, coarse_config(h, nq, kind), nq, k, h->ws.ptr);
     CM_HIP(hipMemcpyAsync(&h->last_fallbacks, w.fb_count, 4, hipMemcpyDeviceToHost, h->stream));
-    if (w.wide_ctr) CM_HIP(hipMemcpyAsync(&h->last_wide, w.wide_ctr + 1, 4, hipMemcpyDeviceToHost, h->stream));
+    if (w.wide_ctr) {
+      CM_HIP(hipMemcpyAsync(&h->last_wide, w.wide_ctr + 1, 4, hipMemcpyDeviceToHost, h->stream));
+      CM_HIP(hipMemcpyAsync(&h->last_band, w.wide_ctr + 2, 8, hipMemcpyDeviceToHost, h->stream));
+    }
   }
   CM_HIP(hipStreamSynchronize(h->stream));
   return CM_OK;

@@ -15,15 +15,17 @@
 //     |(1 - xn.qn) - d~| <= E_r = ||qn|| e_r + max||x~|| e_q + slack,
 // the slack (4e-6) covering the fp32 rounding of d~, of qn / xn against the fp64 normalisation
 // of the exact re-rank, and of E_r itself.  The bound is per ROW: at 10M x 768 the certified band
-// is ~800 rows per query for the bench's E5 queries (a global max||e_r|| gives ~4,000),
-// tools/int8_band.py, profiles/r04_int8_band_rowE.json.
+// was ~800 rows per query for the bench's E5 queries with per-row scales (a global max||e_r|| gives
+// ~4,000; tools/int8_band.py, profiles/r04_int8_band_rowE.json); with the group scales below it is
+// 1,190 rows from kth_up alone and 200 with the re-rank's pilot bound (profiles/rerank_pilot.txt).
 //
 // Pipeline (launch_coarse, kind CM_DENSE_Q8): dense_prep_q8 -> f16 sample seed: K1c MINONLY over a
 // 1/16 row sample of the f16 plane (per group: min coarse distance), seed = the k-th smallest group
 // minimum + K1c's bound E (>= the true k-th distance) -> K1q, the int8 scan: every live + allowed
 // row with d~ - E_r <= seed into its (range, query) buffer -> dense_rerank_q8_kernel, three stages:
-// kth_up = k-th smallest d~ + E_r over the candidates and the int8 band = the candidates with
-// d~ - E_r <= kth_up (it holds every exact top-k row); the f16 band = its rows still certifiable
+// kth_up = k-th smallest d~ + E_r over the candidates, tightened to the k-th exact distance of the
+// rows at or below it (the pilot bound, at the kernel), and the int8 band = the candidates with
+// d~ - E_r <= that bound (it holds every exact top-k row); the f16 band = its rows still certifiable
 // after re-scoring from the f16 plane (skipped when only the plane's sample prefix is held); exact
 // fp64 re-rank of that band from the fp32 rows ->
 // dense_rerank_wide_kernel for the queries whose band exceeds kQBand with complete candidate
@@ -859,20 +861,95 @@ __device__ inline uint32_t block_select_fn(V val, int n, int kk, uint32_t *hist)
 // K1q certification + exact re-rank, one kQRT-thread workgroup per query (see the file comment).
 // 1. buffer offsets; 2. the candidates (lo key, up) gathered into LDS (kQGather of them; a larger
 // set is read from the global buffers in place, L2-resident); 3. kth_up = the k-th smallest up;
-// 4. band = candidates with lo <= kth_up; 5. exact fp64 distances, kQRows band rows per wave at a
-// time with all their loads in flight (the arithmetic -- per-lane strided sums, xor-tree reduction
-// -- is dense_rerank_kernel's, so K1q and K1c return bit-identical distances for a row); 6. top-k
-// by rank.
+// 4. band = candidates with lo <= kth_up (3': or the pilot bound); 5. exact fp64 distances, kQRows
+// band rows per wave at a time with all their loads in flight (the arithmetic -- per-lane strided
+// sums, xor-tree reduction -- is dense_rerank_kernel's, so K1q and K1c return bit-identical
+// distances for a row); 6. top-k by rank.
+//
+// 3'. Pilot bound (without a full f16 plane, where the fp64 stage ranks the whole int8 band -- with
+// the plane that stage re-scores the f16 band, ~k rows, and k pilot rows would double it to save f16
+// reads alone; CM_K1Q_PILOT=0 -> pilot == 0 keeps kth_up alone, A/B).  kth_up ~ d_k + E, so the band
+// lo <= kth_up is d~ <= d_k + 2E wide.  The candidates with up <= kth_up -- k of them plus ties on up
+// -- are live, allowed rows; their exact distances are computed first (the fp64 stage's own function:
+// the same bits), pkey = the k-th smallest of them (order key of the returned float), and the band is
+// formed with bound = min(kth_up, pkey + kQPilotPad): d~ <= d_k + E, half the width.  The pilot rows
+// are scored once: they stay out of the band (marked kQTaken where gathered) and their keys join the
+// band's before the final ranking, so the fp64 stage never scores more rows than without the pilot.
+// Safe: a row of the final top-k has a returned distance <= the k-th
+// smallest returned distance of any k live, allowed rows, so <= pkey; its lo is a certified lower
+// bound of the fp64 distance that value was rounded from, so lo <= pkey + the rounding; hence it is in
+// the band.  The f16 stage and the wide re-rank need only an upper bound of the k-th distance that
+// keeps every top-k row: the wide re-rank takes the tighter fb_bound unchanged.  More than kQSel
+// rows with up <= kth_up (mass ties): no pilot.  The buffer-overflow exit leaves before it.
 constexpr int kQGather = K1Q_RR;
 constexpr int kQRows = 8;
 constexpr int kQRerankLds = kQGather * 12;
+// pkey's padding, in order-key steps (= float ulps).  E_r's 4e-6 slack covers the roundings between
+// lo and the fp64 distance; the one it does not cover is that distance's rounding to the returned
+// float, half an ulp of the result (the fp64 value is never a float denormal: 1 - cos is 0 or a
+// multiple of 2^-53), so one step would do; four cost nothing in band size.
+constexpr uint32_t kQPilotPad = 4;
+constexpr int kQPilotRows = 2;   // pilot rows per wave and load round
+constexpr uint64_t kQTaken = ~0ull;   // a gathered candidate the pilot scored (no key: its row would be 2^32 - 1)
+
+// One wave's share of the exact fp64 stage: the rows src[c], c = c0 + r * stride < n (r < NR),
+// all their loads in flight (past n: row n - 1 again, discarded); per-lane strided sums, xor-tree
+// reduction (dense_rerank_kernel's arithmetic, so K1q and K1c return bit-identical distances for a
+// row); lane 0 writes the key
+// (f32_order(distance), row) to out[c].  out may be src (the pilot): entry c is read and written by
+// one wave, in that order; the clamped read of entry n - 1 by another wave may see that entry's key
+// instead of its row, and a key's low word -- all that is read -- is the row.
+// ld = 768: 12 strided elements per lane, loaded unconditionally (rows are zero past dim, and so
+// is s_q: the extra terms add exact zeros, so the sums equal dense_rerank_kernel's over dim).
+template <int NR, typename R>
+__device__ __forceinline__ void q8_exact_rows(const R *src, int n, int c0, int stride, const float *__restrict__ C,
+                                              int ld, const float *s_q, double qnrm, int lane, uint64_t *out) {
+  constexpr int M = 12;
+  float x[NR][M];
+  uint32_t rows[NR];
+#pragma unroll
+  for (int r = 0; r < NR; ++r) {
+    rows[r] = (uint32_t)src[min(c0 + r * stride, n - 1)];
+    const float *cr = C + (int64_t)rows[r] * ld + lane;
+#pragma unroll
+    for (int m = 0; m < M; ++m) x[r][m] = cr[64 * m];
+  }
+  double dq[NR], dc[NR];
+#pragma unroll
+  for (int r = 0; r < NR; ++r) {
+    dq[r] = 0.0;
+    dc[r] = 0.0;
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      const double xv = (double)x[r][m];
+      dq[r] += xv * (double)s_q[lane + 64 * m];
+      dc[r] += xv * xv;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      dq[r] += __shfl_xor(dq[r], o);
+      dc[r] += __shfl_xor(dc[r], o);
+    }
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+      if (c0 + r * stride < n) {
+        const float dist = (float)(1.0 - dq[r] / ((sqrt(dc[r]) + 1e-30) * (qnrm + 1e-30)));
+        out[c0 + r * stride] = ((uint64_t)f32_order(dist) << 32) | rows[r];
+      }
+  }
+}
+
 __global__ void __launch_bounds__(kQRT) dense_rerank_q8_kernel(
     const uint64_t *__restrict__ keys, const float *__restrict__ ups, const uint32_t *__restrict__ cnts, int n_wg,
     int qs, int k, int nq, const float *__restrict__ C, int ld, int dim, const float *__restrict__ q,
     const float4 *__restrict__ qsc, const _Float16 *__restrict__ Xh, const _Float16 *__restrict__ Qh,
     const float *__restrict__ qnorm, const float *__restrict__ row_norms, float *__restrict__ out_dist,
     int64_t *__restrict__ out_row, int32_t *__restrict__ fb_mask, int32_t *__restrict__ fb_count,
-    uint32_t *__restrict__ fb_bound) {
+    uint32_t *__restrict__ fb_bound, int pilot, unsigned long long *__restrict__ band_ctr) {
   const int qi = blockIdx.x;
   if (qi >= nq) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -956,20 +1033,56 @@ __global__ void __launch_bounds__(kQRT) dense_rerank_q8_kernel(
     }
     return;
   }
+  const double qnrm = (double)qsc[qi].w;
+  // 3'. pilot bound (see above): s_sel / s_nsel are free until the final ranking
+  uint32_t bound = tkey;
+  int npilot = 0;
+  if (pilot && Xh == nullptr && total >= k) {
+    for (int jj = tid; jj < total; jj += kQRT) {
+      if (up_at(jj) <= tkey) {
+        const int p = atomicAdd(&s_nsel, 1);
+        if (p < kQSel) s_sel[p] = (uint64_t)jj;
+      }
+    }
+    __syncthreads();
+    npilot = s_nsel;             // >= k
+    __syncthreads();
+    if (tid == 0) s_nsel = 0;    // as the final ranking expects it (barriers in between)
+    if (npilot <= kQSel) {
+      static_assert(kQSel <= kQRT, "one thread per pilot row");
+      if (tid < npilot) {
+        const int jj = (int)s_sel[tid];
+        s_sel[tid] = (uint32_t)key_at(jj);    // the row; its exact key below
+        if (gathered) g_key[jj] = kQTaken;    // scored here: not a band row (a candidate left in the
+      }                                       // global buffers is told by its up)
+      __syncthreads();
+      // row c on wave c % kQRW: k + ties <= kQRW * kQPilotRows = 32 rows are one round of loads
+      for (int c0 = wave; c0 < npilot; c0 += kQRW * kQPilotRows)
+        q8_exact_rows<kQPilotRows>(s_sel, npilot, c0, kQRW, C, ld, s_q, qnrm, lane, s_sel);
+      __syncthreads();
+      const uint32_t pkey = block_select_fn([&](int i) { return (uint32_t)(s_sel[i] >> 32); }, npilot, k - 1, hist);
+      bound = min(tkey, pkey <= 0xffffffffu - kQPilotPad ? pkey + kQPilotPad : 0xffffffffu);
+    } else {
+      npilot = 0;
+    }
+  }
+  const bool pilot_by_up = npilot > 0 && !gathered;
   for (int jj = tid; jj < total; jj += kQRT) {
     const uint64_t key = key_at(jj);
-    if (tkey == 0xffffffffu || (uint32_t)(key >> 32) <= tkey) {   // lo <= kth_up (order-preserving keys)
+    if (key == kQTaken || (pilot_by_up && up_at(jj) <= tkey)) continue;   // a pilot row
+    if (bound == 0xffffffffu || (uint32_t)(key >> 32) <= bound) {   // lo <= bound (order-preserving keys)
       const int p = atomicAdd(&s_band, 1);
       if (p < kQBand) s_rows[p] = (uint32_t)key;
     }
   }
   __syncthreads();
   const int band = s_band;
-  if (band > kQBand) {   // complete candidate set, band too wide for LDS: the wide re-rank (fb_mask 2)
+  if (band + npilot > kQBand) {   // complete candidate set, band too wide for LDS: the wide re-rank (fb_mask 2)
     if (tid == 0) {
       fb_mask[qi] = 2;
-      fb_bound[qi] = tkey;
+      fb_bound[qi] = bound;
       atomicAdd(fb_count, 1);
+      if (npilot) atomicAdd(band_ctr, (unsigned long long)npilot);
     }
     return;
   }
@@ -1048,55 +1161,17 @@ __global__ void __launch_bounds__(kQRT) dense_rerank_q8_kernel(
   if (band2 > kQBand2) {   // (the f16 band holds the int8 band's near-ties: the wide re-rank)
     if (tid == 0) {
       fb_mask[qi] = 2;
-      fb_bound[qi] = tkey;
+      fb_bound[qi] = bound;
       atomicAdd(fb_count, 1);
     }
     return;
   }
   }   // Xh != nullptr (without it: s_ex = g_key's 64 KiB holds kQBand keys beside s_rows in g_up's space)
-  const double qnrm = (double)qsc[qi].w;
-  // ld = 768: 12 strided elements per lane, loaded unconditionally (rows are zero past dim, and so
-  // is s_q: the extra terms add exact zeros, so the sums equal dense_rerank_kernel's over dim)
-  constexpr int M = 12;
-  for (int c0 = wave * kQRows; c0 < band2; c0 += kQRW * kQRows) {
-    float x[kQRows][M];
-    uint32_t rows[kQRows];
-#pragma unroll
-    for (int r = 0; r < kQRows; ++r) {
-      const int c = min(c0 + r, band2 - 1);
-      rows[r] = band_rows[c];
-      const float *cr = C + (int64_t)rows[r] * ld + lane;
-#pragma unroll
-      for (int m = 0; m < M; ++m) x[r][m] = cr[64 * m];
-    }
-    double dq[kQRows], dc[kQRows];
-#pragma unroll
-    for (int r = 0; r < kQRows; ++r) {
-      dq[r] = 0.0;
-      dc[r] = 0.0;
-#pragma unroll
-      for (int m = 0; m < M; ++m) {
-        const double xv = (double)x[r][m];
-        dq[r] += xv * (double)s_q[lane + 64 * m];
-        dc[r] += xv * xv;
-      }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-      for (int r = 0; r < kQRows; ++r) {
-        dq[r] += __shfl_xor(dq[r], o);
-        dc[r] += __shfl_xor(dc[r], o);
-      }
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (int r = 0; r < kQRows; ++r)
-        if (c0 + r < band2) {
-          const float dist = (float)(1.0 - dq[r] / ((sqrt(dc[r]) + 1e-30) * (qnrm + 1e-30)));
-          s_ex[c0 + r] = ((uint64_t)f32_order(dist) << 32) | rows[r];
-        }
-    }
-  }
+  if (tid == 0) atomicAdd(band_ctr, (unsigned long long)(band2 + npilot));
+  for (int c0 = wave * kQRows; c0 < band2; c0 += kQRW * kQRows)
+    q8_exact_rows<kQRows>(band_rows, band2, c0, 1, C, ld, s_q, qnrm, lane, s_ex);
+  if (tid < npilot) s_ex[band2 + tid] = s_sel[tid];   // the pilot rows' keys join the band's
+  band2 += npilot;
   __syncthreads();
   // top-k of the band: the k-th smallest distance (radix select over the keys' high words), then the
   // rows at or below it (k plus exact distance ties: a handful) ranked by their full keys

@@ -191,6 +191,12 @@ int32_t cm_dense_last_fallbacks(cm_dense *h);
  * rag/retrieval/vector_chroma.py:204-253); 0 for other paths, -1 on error. */
 int32_t cm_dense_workspace_wide_reranks(cm_dense *h, int32_t nq, int32_t k, const void *workspace_dev);
 int32_t cm_dense_last_wide_reranks(cm_dense *h);
+/* K1q/K1q-s: rows whose exact fp64 distance that search's re-rank computed from
+ * the fp32 rows, summed over its queries (the certified band, plus the rows of
+ * the pilot bound; $CM_K1Q_PILOT=0 forms the band without it, A/B); 0 for
+ * other paths, -1 on error.                                              */
+int64_t cm_dense_workspace_band_rows(cm_dense *h, int32_t nq, int32_t k, const void *workspace_dev);
+int64_t cm_dense_last_band_rows(cm_dense *h);
 /* kernel timing (bench roofline): while enabled, every search records HIP
  * events on its launch stream around its scan kernel (K1 / K1c / K1s coarse
  * scan); _drain synchronises on them, writes up to cap elapsed ms values and
