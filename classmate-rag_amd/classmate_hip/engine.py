@@ -106,6 +106,16 @@ def _list_allow_words(allow_words, need: int, sync: bool = True):
     return ab
 
 
+def _list_filter_of(filter_of, nq: int, n_filters: int) -> np.ndarray:
+    """search_lists' filter_of as a contiguous int32 array: (nq,), every entry a bitmap's index."""
+    fo = _c(np.asarray(filter_of), np.int32)
+    if fo.shape != (nq,):
+        raise ValueError(f"filter_of has shape {fo.shape}, need ({nq},)")
+    if nq and (fo.min() < 0 or fo.max() >= n_filters):
+        raise ValueError(f"filter_of entries must be in [0, {n_filters})")
+    return fo
+
+
 class DenseIndex:
     """HBM-resident fp32 corpus + exact cosine top-k (replaces Chroma's HNSW)."""
 
@@ -237,11 +247,7 @@ class DenseIndex:
             qq = q.contiguous()
             nq = qq.shape[0]
             ab = _list_allow_words(allow_words, (self.size + 31) // 32, sync=False)
-            fo = _c(np.asarray(filter_of), np.int32)
-            if fo.shape != (nq,):
-                raise ValueError(f"filter_of has shape {fo.shape}, need ({nq},)")
-            if nq and (fo.min() < 0 or fo.max() >= ab.shape[0]):
-                raise ValueError(f"filter_of entries must be in [0, {ab.shape[0]})")
+            fo = _list_filter_of(filter_of, nq, ab.shape[0])
             dist = torch.empty((nq, k), dtype=torch.float32, device=qq.device)
             rows = torch.empty((nq, k), dtype=torch.int64, device=qq.device)
             if nq:
@@ -255,11 +261,7 @@ class DenseIndex:
         nq = qq.shape[0]
         need = (self.size + 31) // 32
         ab = _list_allow_words(allow_words, need)
-        fo = _c(np.asarray(filter_of), np.int32)
-        if fo.shape != (nq,):
-            raise ValueError(f"filter_of has shape {fo.shape}, need ({nq},)")
-        if nq and (fo.min() < 0 or fo.max() >= ab.shape[0]):
-            raise ValueError(f"filter_of entries must be in [0, {ab.shape[0]})")
+        fo = _list_filter_of(filter_of, nq, ab.shape[0])
         dist = np.empty((nq, k), np.float32)
         rows = np.empty((nq, k), np.int64)
         vecs = np.empty((nq, k, self.dim), np.float32) if return_vectors else None
@@ -639,11 +641,7 @@ class BM25Index:
         flat = np.concatenate([np.asarray(q, np.int32) for q in queries]) if off[-1] else np.zeros(1, np.int32)
         flat = _c(flat, np.int32)
         ab = _list_allow_words(allow_words, (self.num_docs + 31) // 32, sync=not dev)
-        fo = _c(np.asarray(filter_of), np.int32)
-        if fo.shape != (nq,):
-            raise ValueError(f"filter_of has shape {fo.shape}, need ({nq},)")
-        if nq and (fo.min() < 0 or fo.max() >= ab.shape[0]):
-            raise ValueError(f"filter_of entries must be in [0, {ab.shape[0]})")
+        fo = _list_filter_of(filter_of, nq, ab.shape[0])
         if dev:
             if eps_io is not None and eps_io.shape[0] != ab.shape[0]:
                 raise ValueError(f"eps_io has {eps_io.shape[0]} entries for {ab.shape[0]} bitmaps")

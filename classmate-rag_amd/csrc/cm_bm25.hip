@@ -24,6 +24,7 @@
 // scores included, which reproduces the reference's zero-score padding.
 // A tournament kernel merges the sorted per-range lists.
 #include "cm_common.h"
+#include "cm_row_lists.h"
 
 #include <hipcub/hipcub.hpp>
 

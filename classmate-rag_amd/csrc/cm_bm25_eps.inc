@@ -305,42 +305,46 @@ int bm25_eps_multi(cm_bm25 *h, const uint32_t *allow_dev, int n, const int64_t *
     sort_b = std::max(sort_b, std::max(b1, b2));
   }
   // ---- workspace: a buffer of its own (ws, tmp and allow_buf hold a list search's live state) ----
-  size_t o = 0;
-  const auto take = [&o](int64_t bytes) {
-    const size_t at = o;
-    o += (size_t)round_up(std::max<int64_t>(bytes, 16), 256);
-    return at;
-  };
   const int64_t n_entries = n_slices * kBmEpsFilters, n_who = (int64_t)who.size();
-  const size_t rounds_o = take((int64_t)n_rounds * (int64_t)sizeof(BmEpsRound));
-  const size_t res_o = take(n_who * (int64_t)sizeof(BmEpsResult)), flag_o = take(4), memb_o = take(ndocs * 4);
-  // zeroed every round: the cursors, the tuple counts, the table's df
-  const size_t cursor_o = take(kBmEpsFilters * kBmEpsCursorStride * 4), nt_o = take(kBmEpsFilters * 4);
-  const size_t tdf_o = take(n_entries * 4), zero_end = o;
-  // set to ~0 every round: the table's first keys, the tuple slots
-  const size_t tfirst_o = take(n_entries * 8), keys_a_o = take(cap_max * 8), vals_a_o = take(cap_max * 8), ones_end = o;
-  const size_t keys_b_o = take(cap_max * 8), vals_b_o = take(cap_max * 8);
-  const size_t fk_a_o = take(cap_max), fk_b_o = take(cap_max), sort_o = take((int64_t)sort_b);
-  if ((rc = h->eps_ws.ensure(o))) return rc;
-  char *base = h->eps_ws.as<char>();
-  BmEpsRound *rounds_dev = reinterpret_cast<BmEpsRound *>(base + rounds_o);
-  BmEpsResult *res_dev = reinterpret_cast<BmEpsResult *>(base + res_o);
-  int32_t *flag_dev = reinterpret_cast<int32_t *>(base + flag_o);
-  uint32_t *memb = reinterpret_cast<uint32_t *>(base + memb_o);
-  uint32_t *cursor = reinterpret_cast<uint32_t *>(base + cursor_o), *nt = reinterpret_cast<uint32_t *>(base + nt_o);
-  uint32_t *tab_df = reinterpret_cast<uint32_t *>(base + tdf_o);
-  unsigned long long *tab_first = reinterpret_cast<unsigned long long *>(base + tfirst_o);
-  uint64_t *keys_a = reinterpret_cast<uint64_t *>(base + keys_a_o), *vals_a = reinterpret_cast<uint64_t *>(base + vals_a_o);
-  uint64_t *keys_b = reinterpret_cast<uint64_t *>(base + keys_b_o), *vals_b = reinterpret_cast<uint64_t *>(base + vals_b_o);
-  uint8_t *fk_a = reinterpret_cast<uint8_t *>(base + fk_a_o), *fk_b = reinterpret_cast<uint8_t *>(base + fk_b_o);
+  BmEpsRound *rounds_dev;
+  BmEpsResult *res_dev;
+  int32_t *flag_dev;
+  uint32_t *memb, *cursor, *nt, *tab_df;
+  unsigned long long *tab_first;
+  uint64_t *keys_a, *vals_a, *keys_b, *vals_b;
+  uint8_t *fk_a, *fk_b;
+  char *sort_ws;
+  const auto carve = [&](char *base) {   // the bytes it takes
+    Carver c{base};
+    rounds_dev = c.take<BmEpsRound>((size_t)n_rounds);
+    res_dev = c.take<BmEpsResult>((size_t)n_who);
+    flag_dev = c.take<int32_t>(1);
+    memb = c.take<uint32_t>((size_t)ndocs);
+    // zeroed every round: the cursors, the tuple counts, the table's df (cursor up to tab_first)
+    cursor = c.take<uint32_t>(kBmEpsFilters * kBmEpsCursorStride);
+    nt = c.take<uint32_t>(kBmEpsFilters);
+    tab_df = c.take<uint32_t>((size_t)n_entries);
+    // set to ~0 every round: the table's first keys, the tuple slots (tab_first up to keys_b)
+    tab_first = c.take<unsigned long long>((size_t)n_entries);
+    keys_a = c.take<uint64_t>((size_t)cap_max);
+    vals_a = c.take<uint64_t>((size_t)cap_max);
+    keys_b = c.take<uint64_t>((size_t)cap_max);
+    vals_b = c.take<uint64_t>((size_t)cap_max);
+    fk_a = c.take<uint8_t>((size_t)cap_max);
+    fk_b = c.take<uint8_t>((size_t)cap_max);
+    sort_ws = c.take<char>(sort_b);
+    return c.off;
+  };
+  if ((rc = h->eps_ws.ensure(carve(nullptr)))) return rc;
+  carve(h->eps_ws.as<char>());
   double *idf_in = reinterpret_cast<double *>(keys_a), *idf_sorted = reinterpret_cast<double *>(vals_a);   // (free by then)
   CM_HIP(hipMemcpyAsync(rounds_dev, rounds.data(), rounds.size() * sizeof(BmEpsRound), hipMemcpyHostToDevice, h->stream));
   CM_HIP(hipMemsetAsync(flag_dev, 0, 4, h->stream));
   for (int q = 0; q < n_rounds; ++q) {
     const BmEpsRound *r = rounds_dev + q;
     const int64_t cap = rounds[q].seg[rounds[q].n];
-    CM_HIP(hipMemsetAsync(base + cursor_o, 0, zero_end - cursor_o, h->stream));
-    CM_HIP(hipMemsetAsync(base + tfirst_o, 0xff, ones_end - tfirst_o, h->stream));
+    CM_HIP(hipMemsetAsync(cursor, 0, (char *)tab_first - (char *)cursor, h->stream));
+    CM_HIP(hipMemsetAsync(tab_first, 0xff, (char *)keys_b - (char *)tab_first, h->stream));
     hipLaunchKernelGGL(bm25_eps_memb_kernel, dim3((unsigned)ceil_div(ndocs, 256)), dim3(256), 0, h->stream, allow_dev,
                        h->live.as<uint32_t>(), ndocs, r, memb);
     CM_HIP(hipGetLastError());
@@ -352,13 +356,13 @@ int bm25_eps_multi(cm_bm25 *h, const uint32_t *allow_dev, int n, const int64_t *
                        tab_df, tab_first, r, cursor, nt, keys_a, vals_a, flag_dev);
     CM_HIP(hipGetLastError());
     size_t b = sort_b;
-    CM_HIP(hipcub::DeviceRadixSort::SortPairs(base + sort_o, b, keys_a, keys_b, vals_a, vals_b, (int)cap, 0, 32 + doc_bits,
+    CM_HIP(hipcub::DeviceRadixSort::SortPairs(sort_ws, b, keys_a, keys_b, vals_a, vals_b, (int)cap, 0, 32 + doc_bits,
                                               h->stream));
     hipLaunchKernelGGL(bm25_eps_idf_kernel, dim3((unsigned)ceil_div(cap, 256)), dim3(256), 0, h->stream, cap, vals_b, r,
                        h->logtab.as<double>(), fk_a, idf_in);
     CM_HIP(hipGetLastError());
     b = sort_b;
-    CM_HIP(hipcub::DeviceRadixSort::SortPairs(base + sort_o, b, fk_a, fk_b, idf_in, idf_sorted, (int)cap, 0, 6, h->stream));
+    CM_HIP(hipcub::DeviceRadixSort::SortPairs(sort_ws, b, fk_a, fk_b, idf_in, idf_sorted, (int)cap, 0, 6, h->stream));
     hipLaunchKernelGGL(bm25_eps_sum_kernel, dim3((unsigned)rounds[q].n), dim3(64), 0, h->stream, idf_sorted, nt, r, res_dev);
     CM_HIP(hipGetLastError());
   }

@@ -4,12 +4,9 @@
 // candidate statistics, a walk of every query term's whole posting list for its candidate df, the
 // pruned search.  A clause that allows a few thousand rows is answered here from its row list, and
 // every clause of the batch at once:
-//   1. lists  per (filter, word) popcount of allow[f][w] & live[w] (bits at or above ndocs ignored)
-//             and, in the same pass, the sum of dl over those rows (one atomic per workgroup); one
-//             exclusive scan (hipCUB) over all n_filters x n_words counts = the CSR offsets of every
-//             list; the lengths (Nc) and length sums are read back once; a scatter of the ascending
-//             row numbers.  (cm_dense_lists.inc step 1, restated: that file is another translation
-//             unit's, and its count pass has no length sum.)
+//   1. lists  the allowed live rows of every filter as ascending CSR lists and, from the same
+//             pass, the sum of dl over each list (cm_row_lists.h); the lengths (Nc) and length sums
+//             are read back once.
 //   2. df     bm25_list_df_kernel: one workgroup per (filter-term, 256 rows of the filter's list);
 //             a thread looks its row up in the term (list_tf below), one atomic per wave.
 //   3. idf    L[Nc - df] - L[df] from the handle's log table (cm_bm25_prepare_filtered's: glibc
@@ -30,69 +27,6 @@ namespace cm {
 
 constexpr int kBmListChunk = 256;   // rows of one list per workgroup (tests restate it)
 constexpr int kBmListSlots = 64;    // query term descriptors staged in LDS at a time
-
-__device__ inline uint32_t bm_list_word(const uint32_t *__restrict__ allow, const uint32_t *__restrict__ live,
-                                        int64_t ndocs, int64_t n_words, int64_t f, int64_t w) {
-  uint32_t bits = allow[f * n_words + w] & live[w];
-  const int64_t left = ndocs - w * 32;
-  if (left < 32) bits &= (1u << left) - 1u;
-  return bits;
-}
-
-// Workgroup b = (filter b / nbw, words [256 (b % nbw), ...)): cnt[f * n_words + w] = rows of word w
-// that filter f allows and that are live, among rows < ndocs; sum_len[f] += their lengths (zeroed by
-// the caller); cnt[n_filters * n_words] = 0 (the exclusive scan's last element = all list entries).
-__global__ void __launch_bounds__(256) bm25_list_count_kernel(const uint32_t *__restrict__ allow,
-                                                              const uint32_t *__restrict__ live,
-                                                              const int32_t *__restrict__ dl, int64_t ndocs,
-                                                              int64_t n_words, int64_t nbw, int64_t total,
-                                                              int64_t *__restrict__ cnt,
-                                                              unsigned long long *__restrict__ sum_len) {
-  __shared__ unsigned long long red[4];
-  const int64_t f = blockIdx.x / nbw, w = (blockIdx.x % nbw) * 256 + threadIdx.x;
-  unsigned long long sum = 0;
-  if (w < n_words) {
-    uint32_t bits = bm_list_word(allow, live, ndocs, n_words, f, w);
-    cnt[f * n_words + w] = __popc(bits);
-    while (bits) {
-      sum += (unsigned long long)dl[w * 32 + (__ffs(bits) - 1)];
-      bits &= bits - 1;
-    }
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) cnt[total] = 0;
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned long long s = red[0] + red[1] + red[2] + red[3];
-    if (s) atomicAdd(sum_len + f, s);
-  }
-}
-
-// off[f] = prefix[f * n_words] for f <= n_filters: where each list starts (CSR); the length sums
-// follow them in the same buffer, for the one read-back.
-__global__ void __launch_bounds__(256) bm25_list_offsets_kernel(const int64_t *__restrict__ prefix, int64_t n_words,
-                                                                int n_filters, int64_t *__restrict__ off) {
-  const int f = blockIdx.x * 256 + threadIdx.x;
-  if (f <= n_filters) off[f] = prefix[(int64_t)f * n_words];
-}
-
-// rows[prefix[i] + j] = row of the j-th set bit of (filter, word) i: every list ascending.
-__global__ void __launch_bounds__(256) bm25_list_scatter_kernel(const uint32_t *__restrict__ allow,
-                                                                const uint32_t *__restrict__ live, int64_t ndocs,
-                                                                int64_t n_words, int64_t total,
-                                                                const int64_t *__restrict__ prefix,
-                                                                int32_t *__restrict__ rows) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int64_t w = i % n_words;
-  uint32_t bits = bm_list_word(allow, live, ndocs, n_words, i / n_words, w);
-  int64_t o = prefix[i];
-  while (bits) {
-    rows[o++] = (int32_t)(w * 32 + (__ffs(bits) - 1));
-    bits &= bits - 1;
-  }
-}
 
 // tf of (term, row), 0 when the row has no posting of the term.  A term that owns a head tile: the
 // tile's byte (terms with a tf >= 255 own none, so the byte is the tf).  Otherwise a binary search of
@@ -250,70 +184,35 @@ static int bm25_search_lists_impl(const char *fn, bool on_dev, cm_bm25 *h, const
   if (n_filters < 1) CM_FAIL(CM_EINVAL, F + ": n_filters must be >= 1");
   if (!q_terms || !q_off || !allow_bits || !filter_of || !out_score || !out_row || !out_n)
     CM_FAIL(CM_EINVAL, "NULL argument");
-  for (int i = 0; i < nq; ++i)
-    if (filter_of[i] < 0 || filter_of[i] >= n_filters)
-      CM_FAIL(CM_EINVAL, F + ": filter_of[" + std::to_string(i) + "] = " +
-                             std::to_string(filter_of[i]) + " is outside [0, n_filters)");
+  int rc;
+  if ((rc = check_filter_of(F, filter_of, nq, n_filters))) return rc;
   if (q_off[0] < 0) CM_FAIL(CM_EINVAL, "bad q_off");
   for (int i = 0; i < nq; ++i)
     if (q_off[i + 1] < q_off[i]) CM_FAIL(CM_EINVAL, "q_off must be non-decreasing");
   DeviceGuard dg(h->dev);
-  const int64_t ndocs = h->ndocs, nw = ceil_div(ndocs, 32), total = (int64_t)n_filters * nw;
-  if (total + 1 > INT32_MAX)
-    CM_FAIL(CM_EUNSUPPORTED, F + ": n_filters x ceil(ndocs / 32) must stay below 2^31: split the batch");
+  const int64_t ndocs = h->ndocs;
   const int32_t n_slots = q_off[nq];
   h->last_eps_filters = 0;
   h->last_eps_passes = 0;
-  int rc;
   if (on_dev && (rc = stream_wait_stream(h->stream, stream))) return rc;   // the producer of allow_bits
   // ---- 1. lists: count + length sums, scan, one read-back ----
-  std::vector<int64_t> stat(2 * (size_t)n_filters + 1, 0);   // off[0 .. n_filters], then sum_len[0 .. n_filters)
-  int64_t *prefix = nullptr, *off_dev = nullptr;
-  if (total > 0) {
-    size_t scan_b = 0;
-    CM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, (const int64_t *)nullptr, (int64_t *)nullptr,
-                                            (int)(total + 1), h->stream));
-    const size_t cnt_b = (size_t)round_up((total + 1) * 8, 256);
-    const size_t stat_b = (size_t)round_up((int64_t)stat.size() * 8, 256);
-    if ((rc = h->allow_buf.ensure((size_t)total * 4))) return rc;
-    if ((rc = h->tmp.ensure(2 * cnt_b + stat_b + std::max<size_t>(scan_b, 16)))) return rc;
-    char *b = h->tmp.as<char>();
-    int64_t *cnt = reinterpret_cast<int64_t *>(b);
-    prefix = reinterpret_cast<int64_t *>(b + cnt_b);
-    off_dev = reinterpret_cast<int64_t *>(b + 2 * cnt_b);
-    unsigned long long *sum_dev = reinterpret_cast<unsigned long long *>(off_dev + n_filters + 1);
-    CM_HIP(hipMemcpyAsync(h->allow_buf.ptr, allow_bits, (size_t)total * 4, hipMemcpyDefault, h->stream));  // host or device
-    CM_HIP(hipMemsetAsync(sum_dev, 0, (size_t)n_filters * 8, h->stream));
-    const int64_t nbw = ceil_div(nw, 256);
-    hipLaunchKernelGGL(bm25_list_count_kernel, dim3((unsigned)(nbw * n_filters)), dim3(256), 0, h->stream,
-                       h->allow_buf.as<uint32_t>(), h->live.as<uint32_t>(), h->dl.as<int32_t>(), ndocs, nw, nbw, total,
-                       cnt, sum_dev);
-    CM_HIP(hipGetLastError());
-    CM_HIP(hipcub::DeviceScan::ExclusiveSum(b + 2 * cnt_b + stat_b, scan_b, cnt, prefix, (int)(total + 1), h->stream));
-    hipLaunchKernelGGL(bm25_list_offsets_kernel, dim3((unsigned)ceil_div(n_filters + 1, 256)), dim3(256), 0, h->stream,
-                       prefix, nw, n_filters, off_dev);
-    CM_HIP(hipGetLastError());
-    CM_HIP(hipMemcpyAsync(stat.data(), off_dev, stat.size() * 8, hipMemcpyDeviceToHost, h->stream));
-    CM_HIP(hipStreamSynchronize(h->stream));
-  }
-  const int64_t *off = stat.data(), *sum_len = stat.data() + n_filters + 1;
+  RowLists lists;
+  if ((rc = row_lists_count(F, "ndocs", allow_bits, n_filters, h->live.as<uint32_t>(), h->dl.as<int32_t>(), ndocs,
+                            h->allow_buf, h->tmp, h->stream, lists)))
+    return rc;
+  const int64_t *off = lists.stat.data(), *sum_len = off + n_filters + 1, nw = lists.n_words;
   const int64_t n_rows = off[n_filters];
   // ---- the queries' segments (host) ----
-  std::vector<int32_t> seg((size_t)nq + 1, 0);
-  std::vector<uint8_t> used((size_t)n_filters, 0);
+  std::vector<int32_t> seg;
   int64_t n_keys = 0;
   for (int i = 0; i < nq; ++i) {
     const int f = filter_of[i];
     const int64_t nc = off[f + 1] - off[f];
     if (nc > 0 && sum_len[f] == 0)
       CM_FAIL(CM_EZERODIV, "float division by zero (candidate documents have no tokens)");
-    n_keys += nc;
-    if (n_keys > INT32_MAX)
-      CM_FAIL(CM_EUNSUPPORTED, F + ": more than 2^31 (query, row) pairs: split the batch");
-    seg[i + 1] = (int32_t)n_keys;
-    used[f] = 1;
     out_n[i] = (int32_t)std::min<int64_t>(k, nc);
   }
+  if ((rc = row_list_segments(F, off, filter_of, nq, seg, n_keys))) return rc;
   // ---- (filter, distinct known term) pairs of the queries that use the filter, and every slot's ----
   std::vector<int32_t> slot_ft((size_t)std::max(n_slots, 1), -1);
   std::vector<uint64_t> ftkey;
@@ -355,39 +254,46 @@ static int bm25_search_lists_impl(const char *fn, bool on_dev, cm_bm25 *h, const
     CM_HIP(hipcub::DeviceSegmentedRadixSort::SortPairs(
         nullptr, sort_b, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const int32_t *)nullptr, (int32_t *)nullptr,
         (int)n_keys, nq, (const int32_t *)nullptr, (const int32_t *)nullptr, 0, 64, h->stream));
-  size_t o = (size_t)round_up((int64_t)std::max<size_t>(sort_b, 16), 256);
-  const auto take = [&o](int64_t bytes) {
-    const size_t at = o;
-    o += (size_t)round_up(std::max<int64_t>(bytes, 16), 256);
-    return at;
+  char *sort_ws;
+  int32_t *rows, *ftf_dev, *ftt_dev, *neg_dev, *sft_dev, *qoff_dev, *fof_dev, *seg_dev, *vals, *svals;
+  BmListItem *dfi_dev, *sci_dev;
+  unsigned long long *df_dev;
+  double *idf_dev, *eps_dev, *avg_dev, *osc_dev;
+  BmListSlot *slots_dev;
+  uint64_t *keys, *skeys;
+  int64_t *orow_dev;
+  const auto carve = [&](char *base) {   // the bytes it takes
+    Carver c{base};
+    sort_ws = c.take<char>(sort_b);
+    rows = c.take<int32_t>((size_t)n_rows);
+    dfi_dev = c.take<BmListItem>(df_items.size());
+    sci_dev = c.take<BmListItem>(sc_items.size());
+    ftf_dev = c.take<int32_t>((size_t)n_ft);
+    ftt_dev = c.take<int32_t>((size_t)n_ft);
+    df_dev = c.take<unsigned long long>((size_t)n_ft);
+    idf_dev = c.take<double>((size_t)n_ft);
+    neg_dev = c.take<int32_t>((size_t)n_filters);
+    eps_dev = c.take<double>((size_t)n_filters);
+    avg_dev = c.take<double>((size_t)n_filters);
+    sft_dev = c.take<int32_t>((size_t)n_slots);
+    slots_dev = c.take<BmListSlot>((size_t)n_slots);
+    qoff_dev = c.take<int32_t>((size_t)nq + 1);
+    fof_dev = c.take<int32_t>((size_t)nq);
+    seg_dev = c.take<int32_t>((size_t)nq + 1);
+    keys = c.take<uint64_t>((size_t)n_keys);
+    skeys = c.take<uint64_t>((size_t)n_keys);
+    vals = c.take<int32_t>((size_t)n_keys);
+    svals = c.take<int32_t>((size_t)n_keys);
+    osc_dev = c.take<double>((size_t)nq * k);
+    orow_dev = c.take<int64_t>((size_t)nq * k);
+    return c.off;
   };
-  const size_t rows_o = take(n_rows * 4), dfi_o = take((int64_t)df_items.size() * 8);
-  const size_t sci_o = take((int64_t)sc_items.size() * 8), ftf_o = take(n_ft * 4), ftt_o = take(n_ft * 4);
-  const size_t df_o = take(n_ft * 8), idf_o = take(n_ft * 8), neg_o = take((int64_t)n_filters * 4);
-  const size_t eps_o = take((int64_t)n_filters * 8), avg_o = take((int64_t)n_filters * 8);
-  const size_t sft_o = take((int64_t)n_slots * 4), slots_o = take((int64_t)n_slots * (int64_t)sizeof(BmListSlot));
-  const size_t qoff_o = take(((int64_t)nq + 1) * 4), fof_o = take((int64_t)nq * 4), seg_o = take(((int64_t)nq + 1) * 4);
-  const size_t keys_o = take(n_keys * 8), skeys_o = take(n_keys * 8), vals_o = take(n_keys * 4), svals_o = take(n_keys * 4);
-  const size_t osc_o = take((int64_t)nq * k * 8), orow_o = take((int64_t)nq * k * 8);
-  if ((rc = h->ws.ensure(o))) return rc;
+  if ((rc = h->ws.ensure(carve(nullptr)))) return rc;
   if (n_keys > 0 && (rc = bm25_grow_logtab(h, ndocs))) return rc;
-  char *base = h->ws.as<char>();
-  const auto at = [base](size_t x) { return base + x; };
-  int32_t *rows = reinterpret_cast<int32_t *>(at(rows_o));
-  BmListItem *dfi_dev = reinterpret_cast<BmListItem *>(at(dfi_o)), *sci_dev = reinterpret_cast<BmListItem *>(at(sci_o));
-  int32_t *ftf_dev = reinterpret_cast<int32_t *>(at(ftf_o)), *ftt_dev = reinterpret_cast<int32_t *>(at(ftt_o));
-  unsigned long long *df_dev = reinterpret_cast<unsigned long long *>(at(df_o));
-  double *idf_dev = reinterpret_cast<double *>(at(idf_o)), *eps_dev = reinterpret_cast<double *>(at(eps_o));
-  double *avg_dev = reinterpret_cast<double *>(at(avg_o));
-  int32_t *neg_dev = reinterpret_cast<int32_t *>(at(neg_o)), *sft_dev = reinterpret_cast<int32_t *>(at(sft_o));
-  BmListSlot *slots_dev = reinterpret_cast<BmListSlot *>(at(slots_o));
-  int32_t *qoff_dev = reinterpret_cast<int32_t *>(at(qoff_o)), *fof_dev = reinterpret_cast<int32_t *>(at(fof_o));
-  int32_t *seg_dev = reinterpret_cast<int32_t *>(at(seg_o));
-  uint64_t *keys = reinterpret_cast<uint64_t *>(at(keys_o)), *skeys = reinterpret_cast<uint64_t *>(at(skeys_o));
-  int32_t *vals = reinterpret_cast<int32_t *>(at(vals_o)), *svals = reinterpret_cast<int32_t *>(at(svals_o));
+  carve(h->ws.as<char>());
   // (device form: the top-k kernel writes the caller's tensors)
-  double *d_score = on_dev ? out_score : reinterpret_cast<double *>(at(osc_o));
-  int64_t *d_row = on_dev ? out_row : reinterpret_cast<int64_t *>(at(orow_o));
+  double *d_score = on_dev ? out_score : osc_dev;
+  int64_t *d_row = on_dev ? out_row : orow_dev;
   const int32_t *head_id = h->nhead ? h->head_id.as<int32_t>() : (const int32_t *)nullptr;
   std::vector<double> eps((size_t)n_filters, 0.0);   // (host sources of async copies: alive until the last synchronise)
   CM_HIP(hipMemcpyAsync(seg_dev, seg.data(), seg.size() * 4, hipMemcpyHostToDevice, h->stream));
@@ -398,9 +304,7 @@ static int bm25_search_lists_impl(const char *fn, bool on_dev, cm_bm25 *h, const
     CM_HIP(hipMemcpyAsync(sci_dev, sc_items.data(), sc_items.size() * 8, hipMemcpyHostToDevice, h->stream));
     if (n_slots > 0) CM_HIP(hipMemcpyAsync(sft_dev, slot_ft.data(), (size_t)n_slots * 4, hipMemcpyHostToDevice, h->stream));
     // ---- 1b. the lists ----
-    hipLaunchKernelGGL(bm25_list_scatter_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, h->stream,
-                       h->allow_buf.as<uint32_t>(), h->live.as<uint32_t>(), ndocs, nw, total, prefix, rows);
-    CM_HIP(hipGetLastError());
+    if ((rc = row_lists_scatter(lists, h->live.as<uint32_t>(), ndocs, rows, h->stream))) return rc;
     if (n_ft > 0) {
       // ---- 2. candidate df ----
       CM_HIP(hipMemcpyAsync(ftf_dev, ft_filter.data(), (size_t)n_ft * 4, hipMemcpyHostToDevice, h->stream));
@@ -409,12 +313,12 @@ static int bm25_search_lists_impl(const char *fn, bool on_dev, cm_bm25 *h, const
       CM_HIP(hipMemsetAsync(df_dev, 0, (size_t)n_ft * 8, h->stream));
       CM_HIP(hipMemsetAsync(neg_dev, 0, (size_t)n_filters * 4, h->stream));
       hipLaunchKernelGGL(bm25_list_df_kernel, dim3((unsigned)df_items.size()), dim3(256), 0, h->stream, dfi_dev, ftf_dev,
-                         ftt_dev, rows, off_dev, h->term_off.as<int64_t>(), head_id, h->headtf.as<uint8_t>(), h->npad,
+                         ftt_dev, rows, lists.off_dev, h->term_off.as<int64_t>(), head_id, h->headtf.as<uint8_t>(), h->npad,
                          h->post_doc.as<int32_t>(), h->post_tf.as<uint16_t>(), df_dev);
       CM_HIP(hipGetLastError());
       // ---- 3. idf, and the epsilon of the filters that have a negative one ----
       hipLaunchKernelGGL(bm25_list_idf_kernel, dim3((unsigned)ceil_div(n_ft, 256)), dim3(256), 0, h->stream, (int)n_ft,
-                         ftf_dev, off_dev, df_dev, h->logtab.as<double>(), idf_dev, neg_dev);
+                         ftf_dev, lists.off_dev, df_dev, h->logtab.as<double>(), idf_dev, neg_dev);
       CM_HIP(hipGetLastError());
       std::vector<int32_t> neg((size_t)n_filters, 0);
       CM_HIP(hipMemcpyAsync(neg.data(), neg_dev, neg.size() * 4, hipMemcpyDeviceToHost, h->stream));
@@ -457,16 +361,16 @@ static int bm25_search_lists_impl(const char *fn, bool on_dev, cm_bm25 *h, const
     // ---- 4. scores ----
     h->timer.begin(h->stream);
     hipLaunchKernelGGL(bm25_list_score_kernel, dim3((unsigned)sc_items.size()), dim3(256), 0, h->stream, sci_dev, fof_dev,
-                       seg_dev, qoff_dev, slots_dev, rows, off_dev, avg_dev, h->dl.as<int32_t>(), h->headtf.as<uint8_t>(),
+                       seg_dev, qoff_dev, slots_dev, rows, lists.off_dev, avg_dev, h->dl.as<int32_t>(), h->headtf.as<uint8_t>(),
                        h->npad, h->post_doc.as<int32_t>(), h->post_tf.as<uint16_t>(), keys, vals);
     CM_HIP(hipGetLastError());
     h->timer.end(h->stream);
     // ---- 5. top-k ----
-    CM_HIP(hipcub::DeviceSegmentedRadixSort::SortPairs(base, sort_b, keys, skeys, vals, svals, (int)n_keys, nq, seg_dev,
-                                                       seg_dev + 1, 0, 64, h->stream));
+    CM_HIP(hipcub::DeviceSegmentedRadixSort::SortPairs(sort_ws, sort_b, keys, skeys, vals, svals, (int)n_keys, nq,
+                                                       seg_dev, seg_dev + 1, 0, 64, h->stream));
   }
-  hipLaunchKernelGGL(bm25_list_topk_kernel, dim3((unsigned)ceil_div((int64_t)nq * k, 256)), dim3(256), 0, h->stream, skeys,
-                     svals, seg_dev, nq, k, d_score, d_row);
+  hipLaunchKernelGGL(bm25_list_topk_kernel, dim3((unsigned)ceil_div((int64_t)nq * k, 256)), dim3(256), 0, h->stream,
+                     skeys, svals, seg_dev, nq, k, d_score, d_row);
   CM_HIP(hipGetLastError());
   if (!on_dev) {
     CM_HIP(hipMemcpyAsync(out_score, d_score, (size_t)nq * k * 8, hipMemcpyDeviceToHost, h->stream));

@@ -77,6 +77,19 @@ struct DevBuf {
   }
 };
 
+// Carves one buffer into blocks of whole elements, each rounded up to 256 bytes.  A layout is
+// written once, as a function of the base: run with nullptr it sizes the buffer (off = the bytes).
+struct Carver {
+  char *base;
+  size_t off = 0;
+  template <typename T>
+  T *take(size_t n) {
+    T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;  // base == nullptr: sizing pass only
+    off += round_up((int64_t)std::max<size_t>(n, 1) * sizeof(T), 256);
+    return p;
+  }
+};
+
 // Orderable encodings so that an unsigned integer compare gives the float order.
 __host__ __device__ inline uint32_t f32_order(float f) {
   uint32_t u = __builtin_bit_cast(uint32_t, f);

@@ -18,6 +18,7 @@
 // sorted top-k list after every 128-row step.  A second tiny kernel merges the
 // per-range lists (sorted) with a tournament.
 #include "cm_common.h"
+#include "cm_row_lists.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -1310,16 +1311,12 @@ struct DenseWs {
 
 DenseWs dense_ws_layout(const cm_dense *h, const DenseCfg &c, int k, void *base) {
   DenseWs w{};
-  char *p = reinterpret_cast<char *>(base);
-  size_t off = 0;
-  const int nq_pad = c.n_qgroups * c.QB;
-  w.qp = reinterpret_cast<float *>(p + off);
-  off += round_up((int64_t)nq_pad * h->ld * 4, 256);
-  w.invq = reinterpret_cast<float *>(p + off);
-  off += round_up((int64_t)nq_pad * 4, 256);
-  w.cand = reinterpret_cast<uint64_t *>(p + off);
-  off += round_up((int64_t)c.n_qgroups * c.n_cblocks * c.QB * k * 8, 256);
-  w.total = off;
+  Carver cv{reinterpret_cast<char *>(base)};
+  const size_t nq_pad = (size_t)c.n_qgroups * c.QB;
+  w.qp = cv.take<float>(nq_pad * h->ld);
+  w.invq = cv.take<float>(nq_pad);
+  w.cand = cv.take<uint64_t>(nq_pad * c.n_cblocks * k);
+  w.total = cv.off;
   return w;
 }
 
@@ -1672,38 +1669,31 @@ struct CoarseWs {
 };
 CoarseWs coarse_ws_layout(const cm_dense *h, const CoarseCfg &c, int nq, int k, void *base) {
   CoarseWs w{};
-  char *p = reinterpret_cast<char *>(base);
-  size_t off = 0;
-  const int64_t nq_pad = (int64_t)c.n_pass * c.qs;
-  auto take = [&](int64_t bytes) -> char * {
-    char *r = p + off;
-    off += round_up(std::max<int64_t>(bytes, 1), 256);
-    return r;
-  };
+  Carver cv{reinterpret_cast<char *>(base)};
+  const size_t nq_pad = (size_t)c.n_pass * c.qs, n_buf = (size_t)c.n_pass * c.n_wg * c.qs;
   const int cap = c.q8 ? kQCap : kCBufCap;
   if (c.q8) {
-    w.qq = reinterpret_cast<int8_t *>(take(nq_pad * h->ld));
-    w.qsc = reinterpret_cast<float4 *>(take(nq_pad * 16));
+    w.qq = cv.take<int8_t>(nq_pad * h->ld);
+    w.qsc = cv.take<float4>(nq_pad);
   }
-  w.qh = reinterpret_cast<_Float16 *>(take(nq_pad * h->ld * 2));
-  w.qnorm = reinterpret_cast<float *>(take(nq_pad * 16));
-  w.keys = reinterpret_cast<uint64_t *>(take((int64_t)c.n_pass * c.n_wg * c.qs * cap * 8));
-  if (c.q8) w.ups = reinterpret_cast<float *>(take((int64_t)c.n_pass * c.n_wg * c.qs * cap * 4));
-  w.cnt = reinterpret_cast<uint32_t *>(take((int64_t)c.n_pass * c.n_wg * c.qs * 4));
-  w.mins = reinterpret_cast<float *>(take((int64_t)c.n_pass * c.n_wg_sample * c.qs * 4));
-  w.seed = reinterpret_cast<float *>(take(nq_pad * 4));
-  w.fb_mask = reinterpret_cast<int32_t *>(take(nq_pad * 4));
-  w.fb_count = reinterpret_cast<int32_t *>(take(4));
+  w.qh = cv.take<_Float16>(nq_pad * h->ld);
+  w.qnorm = cv.take<float>(nq_pad * 4);
+  w.keys = cv.take<uint64_t>(n_buf * cap);
+  if (c.q8) w.ups = cv.take<float>(n_buf * cap);
+  w.cnt = cv.take<uint32_t>(n_buf);
+  w.mins = cv.take<float>((size_t)c.n_pass * c.n_wg_sample * c.qs);
+  w.seed = cv.take<float>(nq_pad);
+  w.fb_mask = cv.take<int32_t>(nq_pad);
+  w.fb_count = cv.take<int32_t>(1);
   if (c.q8) {
-    w.fb_bound = reinterpret_cast<uint32_t *>(take(nq_pad * 4));
-    w.wide_ctr = reinterpret_cast<int32_t *>(take(16));
-    w.wide_rows = reinterpret_cast<uint32_t *>(take((int64_t)kWideSlots * kWideCap * 4));
-    w.wide_keys = reinterpret_cast<uint64_t *>(take((int64_t)kWideSlots * kWideCap * 8));
+    w.fb_bound = cv.take<uint32_t>(nq_pad);
+    w.wide_ctr = cv.take<int32_t>(4);
+    w.wide_rows = cv.take<uint32_t>((size_t)kWideSlots * kWideCap);
+    w.wide_keys = cv.take<uint64_t>((size_t)kWideSlots * kWideCap);
   }
   const DenseCfg kc = dense_config(h, nq, k, true);
-  w.k1 = dense_ws_layout(h, kc, k, p ? p + off : nullptr);
-  off += w.k1.total;
-  w.total = off;
+  w.k1 = dense_ws_layout(h, kc, k, cv.base ? cv.base + cv.off : nullptr);
+  w.total = cv.off + w.k1.total;
   return w;
 }
 

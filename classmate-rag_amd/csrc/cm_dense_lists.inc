@@ -2,11 +2,9 @@
 // different where clauses (ChromaVectorStore.query, rag/retrieval/vector_chroma.py:204-253, called
 // once per question by the reference).  The scans take one bitmap per launch and stream the whole
 // store for it; a clause that allows a few thousand rows is answered here without a scan:
-//   1. lists  per (filter, word) popcount of allow[f][w] & live[w] (bits at or above size ignored, as
-//             the scans read the last word), one exclusive scan (hipCUB) over all n_filters x n_words
-//             counts = the CSR offsets of every list at once, then a scatter of the row numbers in
-//             ascending order.  The list lengths are read back once (the function's one
-//             synchronisation before its outputs): they size the key buffers.
+//   1. lists  the allowed live rows of every filter as ascending CSR lists (cm_row_lists.h).  The
+//             list lengths are read back once (the function's one synchronisation before its
+//             outputs): they size the key buffers.
 //   2. scan   dense_list_scan_kernel: one workgroup per (filter, kListChunk rows of its list, tile of
 //             up to kListQT of the queries that use it).  The query tile sits in LDS; every wave
 //             gathers whole fp32 rows, kListRowsPerWave at a time, float4 per lane across the dims,
@@ -31,50 +29,6 @@ constexpr int kListLdsBytes = 49152;  // query tile budget: three workgroups per
 __host__ __device__ inline int list_query_tile(int ld) {
   const int fit = kListLdsBytes / (ld * 4);
   return fit < 1 ? 1 : fit > kListQT ? kListQT : fit;
-}
-
-__device__ inline uint32_t list_word(const uint32_t *__restrict__ allow, const uint32_t *__restrict__ live,
-                                     int64_t size, int64_t n_words, int64_t i) {
-  const int64_t w = i % n_words;
-  uint32_t bits = allow[i] & live[w];
-  const int64_t left = size - w * 32;
-  if (left < 32) bits &= (1u << left) - 1u;
-  return bits;
-}
-
-// cnt[f * n_words + w] = rows of word w that filter f allows and that are live, among rows < size;
-// cnt[total] = 0 (so the exclusive scan's last element is the number of all list entries).
-__global__ void __launch_bounds__(256) list_count_kernel(const uint32_t *__restrict__ allow,
-                                                         const uint32_t *__restrict__ live, int64_t size,
-                                                         int64_t n_words, int64_t total, int64_t *__restrict__ cnt) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i > total) return;
-  cnt[i] = i < total ? __popc(list_word(allow, live, size, n_words, i)) : 0;
-}
-
-// off[f] = prefix[f * n_words] for f <= n_filters: where each list starts (CSR), contiguous for the
-// one read-back.
-__global__ void __launch_bounds__(256) list_offsets_kernel(const int64_t *__restrict__ prefix, int64_t n_words,
-                                                           int n_filters, int64_t *__restrict__ off) {
-  const int f = blockIdx.x * 256 + threadIdx.x;
-  if (f <= n_filters) off[f] = prefix[(int64_t)f * n_words];
-}
-
-// rows[prefix[i] + j] = row of the j-th set bit of (filter, word) i: every list ascending.
-__global__ void __launch_bounds__(256) list_scatter_kernel(const uint32_t *__restrict__ allow,
-                                                           const uint32_t *__restrict__ live, int64_t size,
-                                                           int64_t n_words, int64_t total,
-                                                           const int64_t *__restrict__ prefix,
-                                                           uint32_t *__restrict__ rows) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  uint32_t bits = list_word(allow, live, size, n_words, i);
-  const uint32_t r0 = (uint32_t)((i % n_words) * 32);
-  int64_t o = prefix[i];
-  while (bits) {
-    rows[o++] = r0 + (uint32_t)(__ffs(bits) - 1);
-    bits &= bits - 1;
-  }
 }
 
 // One work item of the list scan: list `filter`, its rows [chunk * kListChunk, ...), and the nqt
@@ -201,10 +155,6 @@ __global__ void __launch_bounds__(256) list_topk_kernel(const uint64_t *__restri
   }
 }
 
-}  // namespace cm
-
-namespace cm {
-
 // Padded queries and their fp64 norms from device queries (cm_dense_search_lists_dev): one workgroup
 // per query.  qp[i][0 .. ld) = q[i][0 .. dim) then zeros; qnorm[i] = sqrt of the host loop's sum --
 // s += (double)v * v over the dims in order, ONE sequential chain (a tree gives other bits), the
@@ -250,56 +200,26 @@ static int dense_search_lists_impl(const char *fn, bool on_dev, cm_dense *h, con
   if (k < 1) CM_FAIL(CM_EINVAL, F + ": k must be >= 1");
   if (n_filters < 1) CM_FAIL(CM_EINVAL, F + ": n_filters must be >= 1");
   if (!q || !allow_bits || !filter_of || !out_dist || !out_row) CM_FAIL(CM_EINVAL, "NULL argument");
-  for (int i = 0; i < nq; ++i)
-    if (filter_of[i] < 0 || filter_of[i] >= n_filters)
-      CM_FAIL(CM_EINVAL, F + ": filter_of[" + std::to_string(i) + "] = " +
-                             std::to_string(filter_of[i]) + " is outside [0, n_filters)");
+  int rc;
+  if ((rc = check_filter_of(F, filter_of, nq, n_filters))) return rc;
   if (k > kMaxTopK)
     CM_FAIL(CM_EUNSUPPORTED, F + ": k above cm_max_topk(): use cm_dense_search per clause");
   DeviceGuard dg(h->dev);
-  const int64_t size = h->size, nw = ceil_div(size, 32), total = (int64_t)n_filters * nw;
+  const int64_t size = h->size;
   const int ld = h->ld, dim = h->dim;
-  if (total + 1 > INT32_MAX)
-    CM_FAIL(CM_EUNSUPPORTED, F + ": n_filters x ceil(size / 32) must stay below 2^31: split the batch");
-  int rc;
   if (on_dev && (rc = stream_wait_stream(h->stream, stream))) return rc;   // the producers of q and allow_bits
   // ---- 1. list lengths: count, scan, read back ----
-  std::vector<int64_t> off((size_t)n_filters + 1, 0);
-  int64_t *prefix = nullptr, *off_dev = nullptr;
-  if (total > 0) {
-    size_t scan_b = 0;
-    CM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, (const int64_t *)nullptr, (int64_t *)nullptr,
-                                            (int)(total + 1), h->stream));
-    const size_t cnt_b = (size_t)round_up((total + 1) * 8, 256);
-    const size_t off_b = (size_t)round_up(((int64_t)n_filters + 1) * 8, 256);
-    if ((rc = h->allow_buf.ensure((size_t)total * 4))) return rc;
-    if ((rc = h->rows_buf.ensure(2 * cnt_b + off_b + std::max<size_t>(scan_b, 16)))) return rc;
-    char *b = h->rows_buf.as<char>();
-    int64_t *cnt = reinterpret_cast<int64_t *>(b);
-    prefix = reinterpret_cast<int64_t *>(b + cnt_b);
-    off_dev = reinterpret_cast<int64_t *>(b + 2 * cnt_b);
-    CM_HIP(hipMemcpyAsync(h->allow_buf.ptr, allow_bits, (size_t)total * 4, hipMemcpyDefault, h->stream));  // host or device
-    hipLaunchKernelGGL(list_count_kernel, dim3((unsigned)ceil_div(total + 1, 256)), dim3(256), 0, h->stream,
-                       h->allow_buf.as<uint32_t>(), h->live, size, nw, total, cnt);
-    CM_HIP(hipGetLastError());
-    CM_HIP(hipcub::DeviceScan::ExclusiveSum(b + 2 * cnt_b + off_b, scan_b, cnt, prefix, (int)(total + 1), h->stream));
-    hipLaunchKernelGGL(list_offsets_kernel, dim3((unsigned)ceil_div(n_filters + 1, 256)), dim3(256), 0, h->stream,
-                       prefix, nw, n_filters, off_dev);
-    CM_HIP(hipGetLastError());
-    CM_HIP(hipMemcpyAsync(off.data(), off_dev, off.size() * 8, hipMemcpyDeviceToHost, h->stream));
-    CM_HIP(hipStreamSynchronize(h->stream));
-  }
+  RowLists lists;
+  if ((rc = row_lists_count(F, "size", allow_bits, n_filters, h->live, nullptr, size, h->allow_buf, h->rows_buf, h->stream,
+                            lists)))
+    return rc;
+  const int64_t *off = lists.stat.data();
   // ---- the queries' segments and the work items (host) ----
   const int64_t n_rows = off[n_filters];
-  std::vector<int32_t> seg((size_t)nq + 1, 0), qorder((size_t)nq), qstart((size_t)n_filters + 1, 0);
+  std::vector<int32_t> seg, qorder((size_t)nq), qstart((size_t)n_filters + 1, 0);
   int64_t n_keys = 0;
-  for (int i = 0; i < nq; ++i) {
-    n_keys += off[filter_of[i] + 1] - off[filter_of[i]];
-    if (n_keys > INT32_MAX)
-      CM_FAIL(CM_EUNSUPPORTED, F + ": more than 2^31 (query, row) pairs: split the batch");
-    seg[i + 1] = (int32_t)n_keys;
-    qstart[filter_of[i] + 1] += 1;
-  }
+  if ((rc = row_list_segments(F, off, filter_of, nq, seg, n_keys))) return rc;
+  for (int i = 0; i < nq; ++i) qstart[filter_of[i] + 1] += 1;
   for (int f = 0; f < n_filters; ++f) qstart[f + 1] += qstart[f];
   {
     std::vector<int32_t> fill(qstart.begin(), qstart.end() - 1);
@@ -323,26 +243,31 @@ static int dense_search_lists_impl(const char *fn, bool on_dev, cm_dense *h, con
     CM_HIP(hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, sort_b, (const uint64_t *)nullptr, (uint64_t *)nullptr,
                                                       (int)n_keys, nq, (const int32_t *)nullptr,
                                                       (const int32_t *)nullptr, 0, 64, h->stream));
-  size_t o = (size_t)round_up((int64_t)std::max<size_t>(sort_b, 16), 256);
-  const auto take = [&o](int64_t bytes) {
-    const size_t at = o;
-    o += (size_t)round_up(std::max<int64_t>(bytes, 16), 256);
-    return at;
+  char *sort_ws;
+  uint32_t *rows;
+  ListItem *items_dev;
+  int32_t *qord_dev, *seg_dev;
+  float *qp;
+  double *qn_dev;
+  uint64_t *keys, *sorted;
+  const auto carve = [&](char *base) {   // the bytes it takes; called to size ws first: ensure may move it
+    Carver c{base};
+    sort_ws = c.take<char>(sort_b);
+    rows = c.take<uint32_t>((size_t)n_rows);
+    items_dev = c.take<ListItem>(items.size());
+    qord_dev = c.take<int32_t>((size_t)nq);
+    seg_dev = c.take<int32_t>((size_t)nq + 1);
+    qp = c.take<float>((size_t)nq * ld);
+    qn_dev = c.take<double>((size_t)nq);
+    keys = c.take<uint64_t>((size_t)n_keys);
+    sorted = c.take<uint64_t>((size_t)n_keys);
+    return c.off;
   };
-  const size_t rows_o = take(n_rows * 4), items_o = take((int64_t)items.size() * 16), qord_o = take((int64_t)nq * 4);
-  const size_t seg_o = take(((int64_t)nq + 1) * 4), qp_o = take((int64_t)nq * ld * 4), qn_o = take((int64_t)nq * 8);
-  const size_t keys_o = take(n_keys * 8), sorted_o = take(n_keys * 8);
   const size_t obytes = (size_t)nq * k * (4 + 8);
   const size_t vbytes = out_vec ? (size_t)nq * k * dim * 4 : 0;
-  if ((rc = h->ws.ensure(o))) return rc;
+  if ((rc = h->ws.ensure(carve(nullptr)))) return rc;
   if (!on_dev && (rc = h->out_buf.ensure(round_up(obytes, 256) + vbytes))) return rc;
-  char *base = h->ws.as<char>();
-  uint32_t *rows = reinterpret_cast<uint32_t *>(base + rows_o);
-  ListItem *items_dev = reinterpret_cast<ListItem *>(base + items_o);
-  int32_t *qord_dev = reinterpret_cast<int32_t *>(base + qord_o), *seg_dev = reinterpret_cast<int32_t *>(base + seg_o);
-  float *qp = reinterpret_cast<float *>(base + qp_o);
-  double *qn_dev = reinterpret_cast<double *>(base + qn_o);
-  uint64_t *keys = reinterpret_cast<uint64_t *>(base + keys_o), *sorted = reinterpret_cast<uint64_t *>(base + sorted_o);
+  carve(h->ws.as<char>());
   // (device form: the top-k kernel writes the caller's tensors)
   float *d_dist = on_dev ? out_dist : h->out_buf.as<float>();
   int64_t *d_row = on_dev ? out_row : reinterpret_cast<int64_t *>(h->out_buf.as<char>() + round_up((int64_t)nq * k * 4, 8));
@@ -372,21 +297,19 @@ static int dense_search_lists_impl(const char *fn, bool on_dev, cm_dense *h, con
     CM_HIP(hipMemcpyAsync(qord_dev, qorder.data(), qorder.size() * 4, hipMemcpyHostToDevice, h->stream));
     CM_HIP(hipMemcpyAsync(items_dev, items.data(), items.size() * 16, hipMemcpyHostToDevice, h->stream));
     // ---- 1b. the lists ----
-    hipLaunchKernelGGL(list_scatter_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, h->stream,
-                       h->allow_buf.as<uint32_t>(), h->live, size, nw, total, prefix, rows);
-    CM_HIP(hipGetLastError());
+    if ((rc = row_lists_scatter(lists, h->live, size, rows, h->stream))) return rc;
     // ---- 2. exact keys ----
     h->timer.begin(h->stream);
     hipLaunchKernelGGL(dense_list_scan_kernel, dim3((unsigned)items.size()), dim3(256), (size_t)qt * ld * 4, h->stream,
-                       h->C, ld, rows, off_dev, items_dev, qord_dev, seg_dev, qp, qn_dev, keys);
+                       h->C, ld, rows, lists.off_dev, items_dev, qord_dev, seg_dev, qp, qn_dev, keys);
     CM_HIP(hipGetLastError());
     h->timer.end(h->stream);
     // ---- 3. top-k ----
-    CM_HIP(hipcub::DeviceSegmentedRadixSort::SortKeys(base, sort_b, keys, sorted, (int)n_keys, nq, seg_dev, seg_dev + 1,
-                                                      0, 64, h->stream));
+    CM_HIP(hipcub::DeviceSegmentedRadixSort::SortKeys(sort_ws, sort_b, keys, sorted, (int)n_keys, nq, seg_dev,
+                                                      seg_dev + 1, 0, 64, h->stream));
   }
-  hipLaunchKernelGGL(list_topk_kernel, dim3((unsigned)ceil_div((int64_t)nq * k, 256)), dim3(256), 0, h->stream, sorted,
-                     seg_dev, nq, k, d_dist, d_row);
+  hipLaunchKernelGGL(list_topk_kernel, dim3((unsigned)ceil_div((int64_t)nq * k, 256)), dim3(256), 0, h->stream,
+                     sorted, seg_dev, nq, k, d_dist, d_row);
   CM_HIP(hipGetLastError());
   float *d_vec = nullptr;
   if (out_vec) {

@@ -471,17 +471,6 @@ HostStage &stage() {
   return s;
 }
 
-struct Carver {
-  char *base;
-  size_t off = 0;
-  template <typename T>
-  T *take(size_t n) {
-    T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;  // base == nullptr: sizing pass only
-    off += round_up((int64_t)std::max<size_t>(n, 1) * sizeof(T), 256);
-    return p;
-  }
-};
-
 }  // namespace
 
 // Multi-GPU exchange merge: the packed all-gather of every shard's
