@@ -65,6 +65,10 @@ SIGNATURES = {
     "cm_dense_compact": (c_int, c_vp, c_i64, c_i32, c_vp, c_vp),
     "cm_dense_truncate": (c_int, c_vp, c_i64),
     "cm_dense_reset": (c_int, c_vp),
+    "cm_dense_set_center": (c_int, c_vp, c_vp),
+    "cm_dense_get_center": (c_int, c_vp, c_vp, c_vp),
+    "cm_dense_mean": (c_int, c_vp, c_vp, c_vp),
+    "cm_dense_column_sums": (c_int, c_vp, c_vp, c_vp),
     "cm_dense_live_count": (c_i64, c_vp),
     "cm_dense_size": (c_i64, c_vp),
     "cm_dense_dim": (c_i32, c_vp),

@@ -194,6 +194,38 @@ class DenseIndex:
         """Drop rows >= new_size (cleared as in a never-written store) -- cm_dense_truncate."""
         L.check(L.fn["cm_dense_truncate"](self._h, int(new_size)), "cm_dense_truncate")
 
+    def set_center(self, mu=None):
+        """Centre of the int8 coarse plane (cm_dense_set_center): ``mu`` of dim floats, finite, with
+        norm <= 1, or None to clear it.  Results never depend on it; the re-ranked band does (for
+        E5-like rows whose pairwise cosine is 0.7-0.9, centre on ``mean()``).  Re-quantises the plane."""
+        m = None
+        if mu is not None:
+            m = _c(np.asarray(mu).reshape(-1), np.float32)
+            if m.shape[0] != self.dim:
+                raise ValueError(f"expected a centre of {self.dim} floats, got {m.shape[0]}")
+        L.check(L.fn["cm_dense_set_center"](self._h, L.ptr(m)), "cm_dense_set_center")
+
+    def center(self) -> Optional[np.ndarray]:
+        """The centre set by ``set_center`` (float32, dim), or None."""
+        mu = np.zeros(self.dim, np.float32)
+        is_set = C.c_int32(0)
+        L.check(L.fn["cm_dense_get_center"](self._h, L.ptr(mu), C.byref(is_set)), "cm_dense_get_center")
+        return mu if is_set.value else None
+
+    def column_sums(self):
+        """(fp64 column sums of the normalised live rows, live count) -- cm_dense_column_sums."""
+        sums = np.zeros(self.dim, np.float64)
+        n = C.c_int64(0)
+        L.check(L.fn["cm_dense_column_sums"](self._h, L.ptr(sums), C.byref(n)), "cm_dense_column_sums")
+        return sums, int(n.value)
+
+    def mean(self) -> np.ndarray:
+        """Mean of the normalised live rows (fp64 on the device, rounded to float32); zeros when
+        no row is live -- cm_dense_mean."""
+        mu = np.zeros(self.dim, np.float32)
+        L.check(L.fn["cm_dense_mean"](self._h, L.ptr(mu), None), "cm_dense_mean")
+        return mu
+
     def live_mask(self) -> np.ndarray:
         """Host bool mask of rows [0, size): the live bits alone (no row data is copied)."""
         n = self.size

@@ -267,6 +267,24 @@ class ShardedDenseIndex(_Shards):
                 sh.compact(shrink=True)
         return old_of_new
 
+    def set_center(self, mu=None):
+        """DenseIndex.set_center on every shard: one centre for the whole store."""
+        for sh in self.shards:
+            sh.set_center(mu)
+
+    def center(self) -> Optional[np.ndarray]:
+        return self.shards[0].center()
+
+    def column_sums(self):
+        parts = [sh.column_sums() for sh in self.shards]
+        return sum(p[0] for p in parts), sum(p[1] for p in parts)
+
+    def mean(self) -> np.ndarray:
+        """Mean of the normalised live rows of all shards: their fp64 column sums added (each
+        already weighted by the shard's live count), divided once."""
+        sums, n = self.column_sums()
+        return (sums / n).astype(np.float32) if n else np.zeros(self.dim, np.float32)
+
     def mem_stats(self) -> dict:
         st = [sh.mem_stats() for sh in self.shards]
         return {"bytes": sum(x["bytes"] for x in st), "peak_bytes": sum(x["peak_bytes"] for x in st),

@@ -14,6 +14,8 @@ Chroma persistent dir):
   "metadata"}`` records (``"id": null`` = tombstone), replayed on load, last
   record per row wins;
 * ``meta.json`` -- ``{"format", "dim", "rows"}``, rewritten after every append;
+* ``center.f32`` -- optional: the centre ``recenter()`` set for the int8 coarse plane (dim
+  floats); a cold open sets it on the empty index before the slabs are uploaded;
 * ``snapshot/`` -- the ids, each row's latest record offset in the log and the
   metadata filter columns, valid for a prefix of the log (same inode): a cold
   open reads it plus the records appended after it, and parses a row's
@@ -52,6 +54,7 @@ from .filters import MetaIndex, next_uid, settle_loaded
 
 
 _FORMAT = 2
+_CENTER_FILE = "center.f32"   # the int8 plane's centre (recenter()): dim fp32 values, absent = none
 
 # query_batch(where=[...]): a clause that allows more than size / LIST_CUTOFF_DIV rows is searched
 # by the ordinary scan, once per distinct clause; more selective ones share one row-list search
@@ -174,7 +177,7 @@ def _disk_sig(d: Optional[Path]):
     if d is None:
         return None
     out = []
-    for name in ("meta.json", "rows.log.jsonl", "vectors.f32"):
+    for name in ("meta.json", "rows.log.jsonl", "vectors.f32", _CENTER_FILE):
         try:
             st = os.stat(d / name)
             out.append((st.st_size, st.st_mtime_ns))
@@ -405,6 +408,9 @@ class GpuVectorStore:
             st.line_off[r] = off
         self._index = multidev.new_dense_index(dim, device=self.device, capacity=max(n, 1))
         self._version += 1
+        mu = self._read_center(d, dim)
+        if mu is not None:   # before the upload: the int8 plane is quantised once, under the centre
+            self._index.set_center(mu)
         live = np.fromiter((i is not None for i in ids_), bool, count=n) if n else np.zeros(0, bool)
         if live.any():
             vecs = np.memmap(d / "vectors.f32", dtype=np.float32, mode="r", shape=(n, dim))
@@ -418,6 +424,56 @@ class GpuVectorStore:
                     part = np.nonzero(lv)[0] + s0
                     self._index.upsert(np.asarray(vecs[part], np.float32), part)
             del vecs
+
+    @staticmethod
+    def _read_center(d: Path, dim: int) -> Optional[np.ndarray]:
+        """center.f32 when it holds ``dim`` usable floats, else None (the plain plane)."""
+        try:
+            mu = np.fromfile(d / _CENTER_FILE, dtype=np.float32)
+        except OSError:
+            return None
+        if mu.shape[0] != dim or not np.isfinite(mu).all() or float(np.linalg.norm(mu.astype(np.float64))) > 1.0:
+            return None
+        return mu
+
+    @_locked
+    def recenter(self, mu=None, *, clear: bool = False) -> Dict[str, Any]:
+        """Centre the int8 coarse plane on ``mu`` (default: the mean of the normalised live rows,
+        ``index.mean()``), for E5-like embeddings that share a dominant direction: the certified
+        band of the int8 scans shrinks, results do not change.  Call it after a bulk ingest or
+        from ``vacuum_indexes``; nothing recentres on its own.  ``clear=True`` goes back to the
+        plain plane.  With a directory the centre is kept in
+        ``center.f32`` (removed when cleared) and a cold open applies it.  Returns the live row
+        count and the centre's norm."""
+        self._ensure_loaded()
+        if self._index is None:
+            return {"rows": 0, "norm": 0.0}
+        if clear:
+            self._index.set_center(None)
+            m = None
+        else:
+            m = self._index.mean() if mu is None else np.ascontiguousarray(np.asarray(mu).reshape(-1), np.float32)
+            nrm = float(np.linalg.norm(m.astype(np.float64)))
+            if mu is None and nrm > 1.0:   # identical rows: the fp32 mean of unit vectors, an ulp over
+                m = (m * np.float32((1.0 - 1e-6) / nrm)).astype(np.float32)
+            self._index.set_center(m)
+        self._version += 1
+        d = self._dir
+        if d is not None and (d / "meta.json").exists():
+            if m is None:
+                try:
+                    os.remove(d / _CENTER_FILE)
+                except FileNotFoundError:
+                    pass
+            else:
+                tmp = d / "center.tmp.f32"
+                with open(tmp, "wb") as f:
+                    f.write(m.tobytes())
+                os.replace(tmp, d / _CENTER_FILE)
+            if not self._st.unsaved:
+                self._st.sig = _disk_sig(d)
+        return {"rows": int(self._index.live_count()),
+                "norm": 0.0 if m is None else float(np.linalg.norm(m.astype(np.float64)))}
 
     def _record(self, r: int) -> str:
         _id = self._ids[r]

@@ -1203,6 +1203,9 @@ struct cm_dense {
   int8_t *Xq = nullptr;                    // normalised int8 plane, fragment-major (K1q)
   float2 *rmeta = nullptr;                 // per row {s_r, e_r} of the int8 plane (K1q bound)
   float *rnorm = nullptr;                  // device {max ||Xh_r||, max ||xn_r - Xh_r||, max ||s_r q8_r||, 0}
+  float *mu_dev = nullptr;                 // the int8 plane's centre, ld floats (0 past dim); read when centred
+  bool centred = false;                    // cm_dense_set_center: the int8 plane holds q8(xn - mu)
+  std::vector<float> mu;                   // host copy of the centre (dim floats) when centred
   int path = 0;                            // cm_dense_set_path (0 = automatic)
   int32_t last_fallbacks = -1;             // K1c queries re-run exactly by the last host search
   int32_t last_wide = -1;                  // K1q queries finished by the wide re-rank in the last host search
@@ -1219,6 +1222,9 @@ struct cm_dense {
 };
 
 namespace {
+
+// the centre the int8 plane's kernels read: nullptr = none (the plain plane, bit for bit)
+const float *dense_mu(const cm_dense *h) { return h->centred ? h->mu_dev : nullptr; }
 
 struct DenseCfg {
   int QB, CH, KMAX, n_qgroups, n_cblocks;
@@ -1489,7 +1495,7 @@ int dense_realloc(cm_dense *h, int64_t cap, bool staged) {
                          h->dim, h->ld, a.Xh);
     CM_HIP(hipGetLastError());
     hipLaunchKernelGGL(dense_q8_group_kernel, dim3((unsigned)(keep / 16)), dim3(256), 0, h->stream, a.C, a.invc,
-                       (const int64_t *)nullptr, (int64_t)0, keep / 16, h->dim, h->ld, a.Xq, a.rmeta,
+                       dense_mu(h), (const uint32_t *)a.live, (const int64_t *)nullptr, (int64_t)0, keep / 16, h->dim, h->ld, a.Xq, a.rmeta,
                        reinterpret_cast<uint32_t *>(h->rnorm));
     CM_HIP(hipGetLastError());
     CM_HIP(hipStreamSynchronize(h->stream));
@@ -1650,6 +1656,7 @@ CoarseCfg coarse_config(const cm_dense *h, int nq, int kind) {
 struct CoarseWs {
   int8_t *qq;         // [nq_pad][ld] int8 query fragments (K1q)
   float4 *qsc;        // [nq_pad] {s_q, a_q, b_q, ||q||} (K1q)
+  float *qbase;       // [nq_pad] base_q = 1 - mu.qn of the centred plane, 1.0f without a centre (K1q)
   _Float16 *qh;       // [nq_pad][ld] normalised f16 queries
   float *qnorm;       // [nq_pad][4]
   uint64_t *keys;     // candidate buffers [pass][group][qs][kCBufCap]
@@ -1675,6 +1682,7 @@ CoarseWs coarse_ws_layout(const cm_dense *h, const CoarseCfg &c, int nq, int k, 
   if (c.q8) {
     w.qq = cv.take<int8_t>(nq_pad * h->ld);
     w.qsc = cv.take<float4>(nq_pad);
+    w.qbase = cv.take<float>(nq_pad);
   }
   w.qh = cv.take<_Float16>(nq_pad * h->ld);
   w.qnorm = cv.take<float>(nq_pad * 4);
@@ -1741,7 +1749,7 @@ CoarseFn coarse_kernel(int ld, bool minonly, size_t &lds) {   // K1c, and its dy
   return minonly ? &dense_coarse_scan_kernel<6, 0, true> : &dense_coarse_scan_kernel<6, 0, false>;
 }
 using Q8Fn = void (*)(const int8_t *, const float2 *, const uint32_t *, const uint32_t *, int64_t, const int8_t *,
-                      const float4 *, int, const float *, int64_t, int64_t, int, uint64_t *, float *, uint32_t *);
+                      const float4 *, const float *, int, const float *, int64_t, int64_t, int, uint64_t *, float *, uint32_t *);
 Q8Fn q8_kernel(bool full, size_t &lds) {   // K1q: the full or the shared LDS footprint
   lds = full ? kQLds : kQLdsShared;
   return full ? &dense_q8_scan_kernel<> : &dense_q8_scan_kernel<K1Q_LDS_SHARED>;
@@ -1773,7 +1781,7 @@ int launch_coarse(cm_dense *h, const float *q_dev, int nq, int k, int kind, cons
   if (c.q8) {
     CM_HIP(hipMemsetAsync(w.wide_ctr, 0, 16, st));
     hipLaunchKernelGGL(dense_prep_q8, dim3(c.n_pass * c.qs), dim3(256), 0, st, q_dev, nq, h->dim, h->ld, w.qq, w.qsc,
-                       reinterpret_cast<const uint32_t *>(h->rnorm));
+                       reinterpret_cast<const uint32_t *>(h->rnorm), dense_mu(h), w.qbase);
     CM_HIP(hipGetLastError());
   }
   // 2. sample pre-pass over the f16 plane's sample prefix (per-group minima): K1s or K1c, MINONLY
@@ -1797,14 +1805,15 @@ int launch_coarse(cm_dense *h, const float *q_dev, int nq, int k, int kind, cons
   h->timer.begin(st);
   if (c.q8s) {
     hipLaunchKernelGGL(q8_stream_kernel(nq), dim3((unsigned)ceil_div(c.n_wg, 4)), dim3(256), 0, st, h->Xq, h->rmeta,
-                       h->live, allow, n_words, w.qq, w.qsc, nq, (const float *)w.seed, c.rows_per_wg, c.rows_end,
-                       c.n_wg, w.keys, w.ups, w.cnt);
+                       h->live, allow, n_words, w.qq, w.qsc, (const float *)w.qbase, nq, (const float *)w.seed, c.rows_per_wg,
+                       c.rows_end, c.n_wg, w.keys, w.ups, w.cnt);
   } else if (c.q8) {
     // deferred search (!run_exact): the caller runs other work beside it -> the shared LDS footprint
     // (CM_K1Q_SHARED_LDS=0: the full one, A/B)
     const Q8Fn fn = q8_kernel(run_exact || !env_knob("CM_K1Q_SHARED_LDS", true), lds);
     hipLaunchKernelGGL(fn, dim3(c.n_pass * c.n_wg), dim3(256), lds, st, h->Xq, h->rmeta, h->live, allow, n_words,
-                       w.qq, w.qsc, nq, (const float *)w.seed, c.rows_per_wg, c.rows_end, c.n_wg, w.keys, w.ups, w.cnt);
+                       w.qq, w.qsc, (const float *)w.qbase, nq, (const float *)w.seed, c.rows_per_wg, c.rows_end, c.n_wg,
+                       w.keys, w.ups, w.cnt);
   } else if (c.stream) {
     hipLaunchKernelGGL(stream_kernel(h->ld, nq, false), dim3((unsigned)ceil_div(c.n_wg, 4)), dim3(256), 0, st, h->Xh,
                        h->live, allow, n_words, w.qh, nq, (const float *)w.seed, c.rows_per_wg, c.rows_end, c.n_wg,
@@ -1829,8 +1838,8 @@ int launch_coarse(cm_dense *h, const float *q_dev, int nq, int k, int kind, cons
     // CM_K1Q_WIDE=0: the exact scan takes every failing query, A/B)
     if (env_knob("CM_K1Q_WIDE", true))
       hipLaunchKernelGGL(dense_rerank_wide_kernel, dim3(nq), dim3(kWideThreads), 0, st, w.keys, w.cnt, c.n_wg, c.qs,
-                         k, nq, h->C, h->ld, h->dim, q_dev, w.qsc, xh_full(h) ? h->Xh : nullptr, w.qh, w.qnorm,
-                         h->rnorm, h->Xq, h->rmeta, w.qq, h->live, allow, n_words, c.rows_per_wg, c.rows_end, dist_dev,
+                         k, nq, h->C, h->ld, h->dim, q_dev, w.qsc, (const float *)w.qbase,
+                         xh_full(h) ? h->Xh : nullptr, w.qh, w.qnorm, h->rnorm, h->Xq, h->rmeta, w.qq, h->live, allow, n_words, c.rows_per_wg, c.rows_end, dist_dev,
                          row_dev, w.fb_mask, w.fb_count, w.fb_bound, w.wide_ctr, w.wide_rows, w.wide_keys);
   } else {
     hipLaunchKernelGGL(dense_rerank_kernel, dim3(nq), dim3(256), kGatherCap * 12, st, w.keys, w.cnt, c.n_wg, c.qs, k,
@@ -1949,7 +1958,8 @@ int cm_dense_create(int device, int32_t dim, int64_t capacity, cm_dense **out) {
     delete h;
     CM_FAIL(CM_EDEVICE, "hipStreamCreate failed");
   }
-  if (hipMalloc(&h->rnorm, 16) != hipSuccess || hipMemset(h->rnorm, 0, 16) != hipSuccess) {
+  if (hipMalloc(&h->rnorm, 16) != hipSuccess || hipMemset(h->rnorm, 0, 16) != hipSuccess ||
+      hipMalloc(&h->mu_dev, (size_t)ld * 4) != hipSuccess || hipMemset(h->mu_dev, 0, (size_t)ld * 4) != hipSuccess) {
     cm_dense_destroy(h);
     CM_FAIL(CM_ENOMEM, "dense: out of device memory");
   }
@@ -1968,6 +1978,7 @@ void cm_dense_destroy(cm_dense *h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   dense_free_rows(h);
   if (h->rnorm) (void)hipFree(h->rnorm);
+  if (h->mu_dev) (void)hipFree(h->mu_dev);
   h->timer.release();
   h->staging.release();
   h->rows_buf.release();
@@ -2015,7 +2026,7 @@ int cm_dense_upsert(cm_dense *h, const float *vecs, const int64_t *rows, int64_t
     gs.erase(std::unique(gs.begin(), gs.end()), gs.end());
     CM_HIP(hipMemcpyAsync(h->rows_buf.ptr, gs.data(), gs.size() * 8, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(dense_q8_group_kernel, dim3((unsigned)gs.size()), dim3(256), 0, h->stream, h->C, h->invc,
-                       h->rows_buf.as<int64_t>(), (int64_t)0, (int64_t)gs.size(), h->dim, h->ld, h->Xq, h->rmeta,
+                       dense_mu(h), (const uint32_t *)h->live, h->rows_buf.as<int64_t>(), (int64_t)0, (int64_t)gs.size(), h->dim, h->ld, h->Xq, h->rmeta,
                        reinterpret_cast<uint32_t *>(h->rnorm));
     CM_HIP(hipGetLastError());
     CM_HIP(hipStreamSynchronize(h->stream));
@@ -2046,7 +2057,7 @@ int cm_dense_upsert_dev(cm_dense *h, const float *vecs_dev, int64_t row0, int64_
   // the int8 plane of every row group in the written tiles (rows_alloc is a multiple of 128)
   const int64_t g_lo = (row0 >> 6) * 4, g_hi = ((row0 + n - 1) >> 6) * 4 + 4;
   hipLaunchKernelGGL(dense_q8_group_kernel, dim3((unsigned)(g_hi - g_lo)), dim3(256), 0, st, h->C, h->invc,
-                     (const int64_t *)nullptr, g_lo, g_hi - g_lo, h->dim, h->ld, h->Xq, h->rmeta,
+                     dense_mu(h), (const uint32_t *)h->live, (const int64_t *)nullptr, g_lo, g_hi - g_lo, h->dim, h->ld, h->Xq, h->rmeta,
                      reinterpret_cast<uint32_t *>(h->rnorm));
   CM_HIP(hipGetLastError());
   h->size = std::max(h->size, row0 + n);
@@ -2080,6 +2091,8 @@ int cm_dense_reset(cm_dense *h) {
   CM_HIP(hipMemsetAsync(h->rnorm, 0, 16, h->stream));
   CM_HIP(hipStreamSynchronize(h->stream));
   h->size = 0;
+  h->centred = false;   // a reset store is a never-written one: no centre
+  h->mu.clear();
   return CM_OK;
 }
 

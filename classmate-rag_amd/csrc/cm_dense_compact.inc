@@ -111,6 +111,87 @@ __global__ void __launch_bounds__(256) compact_live_kernel(uint32_t *__restrict_
   live[w] = keep ? (live[w] & mask) : mask;
 }
 
+// Column sums of xn = c * invc (the planes' fp32 normalisation) over the live rows of [0, size), in
+// fp64: the mean a caller hands to cm_dense_set_center.  One workgroup per fixed range of
+// kMeanRowsPerWg rows, wave w its rows 4 i + w, the lanes across a row's float4s (16-byte loads, as
+// compact_gather_kernel), four rows' loads in flight per wave; a dead row is skipped by its live
+// word, which is wave-uniform (one row per wave at a time).  The waves' sums meet in LDS in wave
+// order and go to part[wg][ld]; dense_mean_reduce_kernel adds the workgroups' partials in index
+// order.  No floating-point atomics and a geometry that depends on size alone: two calls on the
+// same store return the same bits.  One pass over the fp32 rows, HBM-bound.
+constexpr int kMeanRowsPerWg = 2048;
+constexpr int kMeanSlots = 8;   // float4 slots per lane: ld <= 2048
+__global__ void __launch_bounds__(256) dense_mean_kernel(const float *__restrict__ C, const float *__restrict__ invc,
+                                                         const uint32_t *__restrict__ live, int64_t size, int ld,
+                                                         double *__restrict__ part) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int ld4 = ld >> 2;
+  const int64_t r0 = (int64_t)blockIdx.x * kMeanRowsPerWg;
+  const int64_t r1 = min(r0 + kMeanRowsPerWg, size);
+  double acc[kMeanSlots][4];
+#pragma unroll
+  for (int s = 0; s < kMeanSlots; ++s)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[s][e] = 0.0;
+  constexpr int U = 4;   // rows in flight per wave
+  for (int64_t rb = r0 + wave; rb < r1; rb += 4 * U) {
+    int64_t r[U];
+    bool on[U];
+    float inv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      r[u] = rb + 4 * u;
+      on[u] = r[u] < r1 && ((live[r[u] >> 5] >> (r[u] & 31)) & 1u);   // wave-uniform
+      inv[u] = on[u] ? invc[r[u]] : 0.f;
+    }
+#pragma unroll
+    for (int s = 0; s < kMeanSlots; ++s) {
+      const int c = lane + 64 * s;
+      if (c < ld4) {
+        f32x4 v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+          v[u] = on[u] ? reinterpret_cast<const f32x4 *>(C + r[u] * ld)[c] : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+          if (on[u]) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[s][e] += (double)(v[u][e] * inv[u]);
+          }
+      }
+    }
+  }
+  __shared__ double s_sum[3][2048];   // waves 1-3; wave 0 adds them in order
+  if (wave > 0) {
+#pragma unroll
+    for (int s = 0; s < kMeanSlots; ++s)
+      if (lane + 64 * s < ld4) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s_sum[wave - 1][4 * (lane + 64 * s) + e] = acc[s][e];
+      }
+  }
+  __syncthreads();
+  if (wave == 0) {
+#pragma unroll
+    for (int s = 0; s < kMeanSlots; ++s)
+      if (lane + 64 * s < ld4) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int col = 4 * (lane + 64 * s) + e;
+          part[(int64_t)blockIdx.x * ld + col] = ((acc[s][e] + s_sum[0][col]) + s_sum[1][col]) + s_sum[2][col];
+        }
+      }
+  }
+}
+__global__ void __launch_bounds__(256) dense_mean_reduce_kernel(const double *__restrict__ part, int n_wg, int ld,
+                                                                double *__restrict__ sums) {
+  const int col = blockIdx.x * 256 + threadIdx.x;
+  if (col >= ld) return;
+  double t = 0.0;
+  for (int w = 0; w < n_wg; ++w) t += part[(int64_t)w * ld + col];
+  sums[col] = t;
+}
+
 }  // namespace cm
 
 namespace {
@@ -156,7 +237,7 @@ int dense_truncate_stream(cm_dense *h, int64_t n, bool fill_live) {
                          hi - n, h->dim, h->ld, h->Xh);
     CM_HIP(hipGetLastError());
     hipLaunchKernelGGL(dense_q8_group_kernel, dim3(4), dim3(256), 0, h->stream, h->C, h->invc,
-                       (const int64_t *)nullptr, (n >> 6) * 4, (int64_t)4, h->dim, h->ld, h->Xq, h->rmeta,
+                       dense_mu(h), (const uint32_t *)h->live, (const int64_t *)nullptr, (n >> 6) * 4, (int64_t)4, h->dim, h->ld, h->Xq, h->rmeta,
                        reinterpret_cast<uint32_t *>(h->rnorm));
     CM_HIP(hipGetLastError());
   }
@@ -275,7 +356,7 @@ int cm_dense_compact(cm_dense *h, int64_t expect_live, int32_t shrink, int64_t *
     const int64_t g_lo = (t0 >> 6) * 4, g_hi = (n >> 6) * 4;
     if (g_lo < g_hi)
       hipLaunchKernelGGL(dense_q8_group_kernel, dim3((unsigned)(g_hi - g_lo)), dim3(256), 0, h->stream, h->C, h->invc,
-                         (const int64_t *)nullptr, g_lo, g_hi - g_lo, h->dim, h->ld, h->Xq, h->rmeta,
+                         dense_mu(h), (const uint32_t *)nullptr, (const int64_t *)nullptr, g_lo, g_hi - g_lo, h->dim, h->ld, h->Xq, h->rmeta,
                          reinterpret_cast<uint32_t *>(h->rnorm));
     CM_HIP(hipGetLastError());
     // ---- 4. live bits and the tail ----
@@ -285,6 +366,87 @@ int cm_dense_compact(cm_dense *h, int64_t expect_live, int32_t shrink, int64_t *
   }
   if (new_size) *new_size = n;
   if (shrink) return dense_shrink(h);
+  return CM_OK;
+}
+
+// The int8 plane's centre (cm_dense_q8.inc, "Centred plane").  Every group that was ever written is
+// re-quantised in this call, which is what makes zeroing rnorm[2] (otherwise never lowered) safe: the
+// groups above hold only code 0 and add nothing to it.
+int cm_dense_set_center(cm_dense *h, const float *mu) {
+  if (!h) CM_FAIL(CM_EINVAL, "null handle");
+  if (mu) {
+    double n2 = 0.0;
+    for (int c = 0; c < h->dim; ++c) {
+      if (!std::isfinite(mu[c])) CM_FAIL(CM_EINVAL, "cm_dense_set_center: non-finite entry");
+      n2 += (double)mu[c] * (double)mu[c];
+    }
+    if (!(n2 <= 1.0)) CM_FAIL(CM_EINVAL, "cm_dense_set_center: ||mu|| must be <= 1");
+  }
+  DeviceGuard dg(h->dev);
+  CM_HIP(hipDeviceSynchronize());   // searches and device upserts run on the callers' streams
+  std::vector<float> pad((size_t)h->ld, 0.f);
+  if (mu) std::copy(mu, mu + h->dim, pad.begin());
+  CM_HIP(hipMemcpyAsync(h->mu_dev, pad.data(), (size_t)h->ld * 4, hipMemcpyHostToDevice, h->stream));
+  h->centred = mu != nullptr;
+  if (mu) h->mu.assign(mu, mu + h->dim);
+  else h->mu.clear();
+  const int64_t extent = std::min<int64_t>(round_up(h->size, kStepRows), h->rows_alloc);  // rows ever written
+  if (extent > 0) {
+    CM_HIP(hipMemsetAsync(h->rnorm + 2, 0, 4, h->stream));
+    hipLaunchKernelGGL(dense_q8_group_kernel, dim3((unsigned)(extent / 16)), dim3(256), 0, h->stream, h->C, h->invc,
+                       dense_mu(h), (const uint32_t *)h->live, (const int64_t *)nullptr, (int64_t)0, extent / 16, h->dim, h->ld, h->Xq, h->rmeta,
+                       reinterpret_cast<uint32_t *>(h->rnorm));
+    CM_HIP(hipGetLastError());
+  }
+  CM_HIP(hipStreamSynchronize(h->stream));   // (pad is read by the copy until here)
+  return CM_OK;
+}
+
+int cm_dense_get_center(cm_dense *h, float *mu_out, int32_t *is_set) {
+  if (!h) CM_FAIL(CM_EINVAL, "null handle");
+  if (is_set) *is_set = h->centred ? 1 : 0;
+  if (mu_out)
+    for (int c = 0; c < h->dim; ++c) mu_out[c] = h->centred ? h->mu[(size_t)c] : 0.f;
+  return CM_OK;
+}
+
+int cm_dense_column_sums(cm_dense *h, double *sums_out, int64_t *n_live_out) {
+  if (!h) CM_FAIL(CM_EINVAL, "null handle");
+  if (!sums_out) CM_FAIL(CM_EINVAL, "cm_dense_column_sums: sums_out is NULL");
+  DeviceGuard dg(h->dev);
+  CM_HIP(hipDeviceSynchronize());   // device upserts run on the callers' streams
+  const int64_t n_live = cm_dense_live_count(h);
+  if (n_live < 0) CM_FAIL(CM_EDEVICE, "cm_dense_column_sums: live count failed");
+  if (n_live_out) *n_live_out = n_live;
+  std::fill(sums_out, sums_out + h->dim, 0.0);
+  if (n_live == 0) return CM_OK;
+  const int n_wg = (int)ceil_div(h->size, kMeanRowsPerWg);
+  ScopedDevBuf part;
+  int rc;
+  if ((rc = part.ensure(((size_t)n_wg + 1) * h->ld * 8))) return rc;
+  double *pd = part.as<double>(), *sums = pd + (size_t)n_wg * h->ld;
+  h->timer.begin(h->stream);
+  hipLaunchKernelGGL(dense_mean_kernel, dim3((unsigned)n_wg), dim3(256), 0, h->stream, h->C, h->invc, h->live, h->size,
+                     h->ld, pd);
+  CM_HIP(hipGetLastError());
+  hipLaunchKernelGGL(dense_mean_reduce_kernel, dim3((unsigned)ceil_div(h->ld, 256)), dim3(256), 0, h->stream, pd, n_wg,
+                     h->ld, sums);
+  CM_HIP(hipGetLastError());
+  h->timer.end(h->stream);
+  CM_HIP(hipMemcpyAsync(sums_out, sums, (size_t)h->dim * 8, hipMemcpyDeviceToHost, h->stream));
+  CM_HIP(hipStreamSynchronize(h->stream));
+  return CM_OK;
+}
+
+int cm_dense_mean(cm_dense *h, float *mean_out, int64_t *n_live_out) {
+  if (!h) CM_FAIL(CM_EINVAL, "null handle");
+  if (!mean_out) CM_FAIL(CM_EINVAL, "cm_dense_mean: mean_out is NULL");
+  std::vector<double> sums((size_t)h->dim);
+  int64_t n = 0;
+  const int rc = cm_dense_column_sums(h, sums.data(), &n);
+  if (rc) return rc;
+  for (int c = 0; c < h->dim; ++c) mean_out[c] = n > 0 ? (float)(sums[(size_t)c] / (double)n) : 0.f;
+  if (n_live_out) *n_live_out = n;
   return CM_OK;
 }
 

@@ -19,6 +19,34 @@
 // ~4,000; tools/int8_band.py, profiles/r04_int8_band_rowE.json); with the group scales below it is
 // 1,190 rows from kth_up alone and 200 with the re-rank's pilot bound (profiles/rerank_pilot.txt).
 //
+// Centred plane (cm_dense_set_center).  Embedding models such as E5 put every vector near one
+// dominant direction (pairwise cosine 0.7-0.9): the distances around the k-th best then spread
+// several times less than on isotropic rows while e_r stays what it was, and the band grows until
+// the (range, query) buffers overflow.  With a centre mu (dim floats, ||mu|| <= 1, usually the mean
+// of the normalised rows) the plane stores q8(y), y = fl32(xn - mu), and rmeta, the group scale and
+// rnorm[2] are those of y; dense_prep_q8 adds the constant back per query: m_q = mu.qn (fp64, from
+// the fp32 qn), base_q = fl32(1 - m_q), and the scans' coarse distance is d~ = base_q - s_q s_r acc.
+// xn.qn = y.qn + mu.qn + (xn - mu - y).qn, so the bound keeps its form with e_r, max||x~|| of y:
+// both shrink with ||xn - mu|| ~ sqrt(1 - cos), and m_q is one constant per query, so the order of
+// the coarse distances is that of y.qn.  The seed, every key and the re-rank stay in true-distance
+// space and read uncentred data (f16 plane, fp32 rows).
+// A row whose fp32 data is all zero (never written, truncated, or a stored zero vector) has xn = 0,
+// true distance 1: it gets code 0 (d~ = base_q, off by |m_q| <= ||mu|| ||qn||) and e_r = ||mu||, and
+// stays out of its group's scale, which |mu| would otherwise set for every partly filled group
+// (a dead zero row, a hole, gets e_r = 0: dense_q8_group_kernel).
+// Slack with a centre, added to a_q on top of the 4e-6 (5e-7, dense_prep_q8):
+//   y = fl32(xn - mu), one rounding per component (__fsub_rn, never contracted with xn = c invc):
+//     |y_c - (xn_c - mu_c)| <= 2^-24 |xn_c - mu_c|, on the dot product <= 2^-24 ||xn - mu|| ||qn||
+//     <= 2^-24 * 2 * (1 + 1e-6)                                                   < 1.2e-7;
+//   m_q: the term qn-against-the-fp64-normalisation is the plain plane's xn.(q^ - qn), already in the
+//     4e-6 (xn.q^ = xn.(q^ - qn) + y.qn + mu.qn + ...: mu multiplies the same fp32 qn the codes were
+//     made from), so only the fp64 sum's own rounding is new: <= 768 * 2^-53 * ||mu|| ||qn||  < 1e-13;
+//   base_q = fl32(1 - m_q), |1 - m_q| <= 2 + 1e-6:                  <= 2^-24 * 2.01  < 1.2e-7;
+//   base_q - a_q and B = base_q - a_q - b_q E now reach 2 where 1 - a_q stayed below 1: each of the
+//     two fp32 roundings can double, + 2 * 2^-24                                  < 1.2e-7.
+//   Sum < 3.7e-7, taken as 5e-7.  (lo = B - A acc itself already ranged over [0, 2].)
+// Without a centre base_q = 1.0f exactly and no bit of any plane, workspace value or result changes.
+//
 // Pipeline (launch_coarse, kind CM_DENSE_Q8): dense_prep_q8 -> f16 sample seed: K1c MINONLY over a
 // 1/16 row sample of the f16 plane (per group: min coarse distance), seed = the k-th smallest group
 // minimum + K1c's bound E (>= the true k-th distance) -> K1q, the int8 scan: every live + allowed
@@ -158,6 +186,8 @@ __host__ __device__ inline int64_t q8_group_row(int64_t G, int i) {   // row i (
   return (G >> 2) * 64 + 16 * (i >> 2) + 4 * (G & 3) + (i & 3);
 }
 __global__ void __launch_bounds__(256) dense_q8_group_kernel(const float *__restrict__ C, const float *__restrict__ invc,
+                                                             const float *__restrict__ mu,
+                                                             const uint32_t *__restrict__ live,
                                                              const int64_t *__restrict__ groups, int64_t g0, int64_t ng,
                                                              int dim, int ld, int8_t *__restrict__ Xq,
                                                              float2 *__restrict__ rmeta, uint32_t *__restrict__ rnorm) {
@@ -169,18 +199,36 @@ __global__ void __launch_bounds__(256) dense_q8_group_kernel(const float *__rest
   const float inv = invc[r];
   const float *crow = C + r * ld;
   auto xn_of = [&](int c) { return c < dim ? crow[c] * inv : 0.f; };  // == the f16 plane's xn
+  // the quantised vector: xn, or xn - mu under a centre (mu: ld floats, 0 past dim; nullptr = none)
+  auto y_of = [&](int c) { return mu ? __fsub_rn(xn_of(c), mu[c]) : xn_of(c); };
   __shared__ float redf[4];
   float amax = 0.f;
-  for (int c = l; c < ld; c += 16) amax = fmaxf(amax, fabsf(xn_of(c)));
+  for (int c = l; c < ld; c += 16) amax = fmaxf(amax, fabsf(y_of(c)));
+  // centred: an all-zero row (never written, truncated, a zero vector) keeps code 0 and stays out of
+  // the group's scale; live, it gets the honest bound e_r = ||mu||; dead (a hole: it can come to
+  // life only through an upsert, which re-quantises its group), e_r = 0 -- the scans take the
+  // largest e_r of a lane's 16 rows for all of them, so a hole's ||mu|| would make candidates of its
+  // 15 group mates in every search.  live == nullptr: every row counts as live (the compaction's
+  // moved rows, whose bits are set after this kernel).
+  bool zero = false, dead = false;
+  if (mu) {   // block-uniform
+    float xmax = 0.f;
+    for (int c = l; c < ld; c += 16) xmax = fmaxf(xmax, fabsf(xn_of(c)));
+    for (int o = 8; o > 0; o >>= 1) xmax = fmaxf(xmax, __shfl_xor(xmax, o));
+    zero = xmax == 0.f;
+    dead = zero && live && !((live[r >> 5] >> (r & 31)) & 1u);
+    if (zero) amax = 0.f;
+  }
   amax = block256_max(amax, redf);
   const float s = amax > 0.f ? amax / 127.f : 1.f;
   double er = 0.0, nr = 0.0;
   for (int c = l; c < ld; c += 16) {
-    const float x = xn_of(c);
-    const int q = max(-127, min(127, (int)rintf(x / s)));
+    const float x = y_of(c);
+    const int q = zero ? 0 : max(-127, min(127, (int)rintf(x / s)));
     Xq[q8_plane_off(r, c, ld)] = (int8_t)q;
     const double xt = (double)s * (double)q;  // exact in fp64
-    er += ((double)x - xt) * ((double)x - xt);
+    const double d = zero ? (dead ? 0.0 : (double)mu[c]) : (double)x - xt;   // zero row: d~ = base_q is off by mu.qn
+    er += d * d;
     nr += xt * xt;
   }
   for (int o = 8; o > 0; o >>= 1) {
@@ -195,10 +243,13 @@ __global__ void __launch_bounds__(256) dense_q8_group_kernel(const float *__rest
 
 // Queries: qn = q / (||q|| + 1e-30) in fp32 (dense_prep_planes' normalisation), its codes in the
 // fragment layout, and qsc = {s_q, a_q, b_q, ||q||}: E_r = a_q + b_q e_r with
-// a_q = max||x~|| e_q + 4e-6 and b_q = ||qn|| (both rounded up).  Padded queries (>= nq): zeros.
+// a_q = max||x~|| e_q + 4e-6 (+ 5e-7 under a centre: the header's derivation) and b_q = ||qn|| (both
+// rounded up); qbase = base_q = fl32(1 - mu.qn), 1.0f without a centre (mu == nullptr).  Padded
+// queries (>= nq): zeros (base 1).
 __global__ void __launch_bounds__(256) dense_prep_q8(const float *__restrict__ q, int nq, int dim, int ld,
                                                      int8_t *__restrict__ Qq, float4 *__restrict__ qsc,
-                                                     const uint32_t *__restrict__ rnorm) {
+                                                     const uint32_t *__restrict__ rnorm,
+                                                     const float *__restrict__ mu, float *__restrict__ qbase) {
   const int qi = blockIdx.x;
   const float *src = q + (int64_t)qi * dim;
   __shared__ double redd[4];
@@ -221,11 +272,17 @@ __global__ void __launch_bounds__(256) dense_prep_q8(const float *__restrict__ q
     t += x * x;
   }
   t = block256_sum(t, redd);
+  double mq = 0.0;   // mu.qn
+  if (mu) {          // uniform
+    for (int c = threadIdx.x; c < ld; c += 256) mq += (double)mu[c] * (double)xn_of(c);
+    mq = block256_sum(mq, redd);
+  }
   if (threadIdx.x == 0) {
     const double nmax = (double)__uint_as_float(rnorm[2]);
-    const float a = (float)(nmax * (double)m.y * (1.0 + 1e-6) + 4e-6);
+    const float a = (float)(nmax * (double)m.y * (1.0 + 1e-6) + (mu ? 4e-6 + 5e-7 : 4e-6));
     const float b = (float)(sqrt(t) * (1.0 + 1e-6));
     qsc[qi] = make_float4(m.x, a, b, sqrtf(tt));
+    qbase[qi] = mu ? (float)(1.0 - mq) : 1.0f;
   }
 }
 
@@ -239,7 +296,7 @@ __global__ void __launch_bounds__(256) dense_prep_q8(const float *__restrict__ q
 // Epilogue per tile (v6).  Lane (g, j) holds the products of query qt * 16 + j with the 16 rows of
 // its row group (16 rt + 4 g + r), which share one scale S (dense_q8_group_kernel).  With E = the
 // group's largest e_r, every row's bounds d~ - E_r >= lo_r = B - A acc_r and d~ + E_r <= lo_r + W,
-// A = s_q S, B = 1 - a_q - b_q E, W = 2 (a_q + b_q E) + 1e-6 (E >= e_r: valid, ~5 % looser than
+// A = s_q S, B = base_q - a_q - b_q E, W = 2 (a_q + b_q E) + 1e-6 (E >= e_r: valid, ~5 % looser than
 // the row's own e_r, which is nearly the group's under a shared scale), so one integer max3 tree
 // per (lane, q-tile) decides the whole lane:
 // no row of the lane passes lo_r <= seed unless B - A max acc <= seed (the same fp32 expression,
@@ -270,7 +327,8 @@ template <int LDS = K1Q_LDS>
 __global__ void __launch_bounds__(256, 1)
     dense_q8_scan_kernel(const int8_t *__restrict__ Xq, const float2 *__restrict__ rmeta,
                          const uint32_t *__restrict__ live, const uint32_t *__restrict__ allow, int64_t n_words,
-                         const int8_t *__restrict__ Qq, const float4 *__restrict__ qsc, int nq,
+                         const int8_t *__restrict__ Qq, const float4 *__restrict__ qsc,
+                         const float *__restrict__ qbase, int nq,
                          const float *__restrict__ seed, int64_t rows_per_wg, int64_t rows_end, int n_wg,
                          uint64_t *__restrict__ out_keys, float *__restrict__ out_up,
                          uint32_t *__restrict__ out_cnt) {
@@ -303,7 +361,7 @@ __global__ void __launch_bounds__(256, 1)
     for (int kh = 0; kh < 2; ++kh)
 #pragma unroll
       for (int qt = 0; qt < QT; ++qt) asm volatile("" : "+a"(qf[c][kh][qt]));
-  // per q-tile constants of the lane's query: s_q, 1 - a_q, a_q, b_q, seed (-inf when padded)
+  // per q-tile constants of the lane's query: s_q, base_q - a_q, a_q, b_q, seed (-inf when padded)
   float sq[QT], oaq[QT], aq[QT], bq[QT], sdq[QT];
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
@@ -311,7 +369,7 @@ __global__ void __launch_bounds__(256, 1)
     const float4 v = qsc[qq];
     sq[qt] = v.x;
     aq[qt] = v.y;
-    oaq[qt] = 1.0f - v.y;
+    oaq[qt] = qbase[qq] - v.y;   // base_q - a_q (base_q = 1.0f without a centre)
     bq[qt] = v.z;
     sdq[qt] = qq < nq ? seed[qq] : -__builtin_inff();
   }
@@ -635,7 +693,8 @@ template <int QT, int R>
 __global__ void __launch_bounds__(256, 1)
     dense_q8_stream_kernel(const int8_t *__restrict__ Xq, const float2 *__restrict__ rmeta,
                            const uint32_t *__restrict__ live, const uint32_t *__restrict__ allow, int64_t n_words,
-                           const int8_t *__restrict__ Qq, const float4 *__restrict__ qsc, int nq,
+                           const int8_t *__restrict__ Qq, const float4 *__restrict__ qsc,
+                           const float *__restrict__ qbase, int nq,
                            const float *__restrict__ seed, int64_t rows_per_vg, int64_t rows_end, int n_vg,
                            uint64_t *__restrict__ out_keys, float *__restrict__ out_up,
                            uint32_t *__restrict__ out_cnt) {
@@ -650,6 +709,19 @@ __global__ void __launch_bounds__(256, 1)
   const int ntiles = r_begin < r_end ? (int)((r_end - r_begin) >> 6) : 0;
   const int total = ntiles * KC;
 
+  float sq[QT], oaq[QT], aq[QT], bq[QT], sdq[QT];
+  uint32_t qcnt[QT];
+#pragma unroll
+  for (int qt = 0; qt < QT; ++qt) {
+    const int qq = qt * 16 + j;
+    const float4 v = qsc[qq];
+    sq[qt] = v.x;
+    aq[qt] = v.y;
+    oaq[qt] = qbase[qq] - v.y;   // base_q - a_q (base_q = 1.0f without a centre)
+    bq[qt] = v.z;
+    sdq[qt] = qq < nq ? seed[qq] : -__builtin_inff();
+    qcnt[qt] = 0u;
+  }
   i32x4q qf[KC][2][QT];
 #pragma unroll
   for (int c = 0; c < KC; ++c)
@@ -664,19 +736,6 @@ __global__ void __launch_bounds__(256, 1)
     for (int kh = 0; kh < 2; ++kh)
 #pragma unroll
       for (int qt = 0; qt < QT; ++qt) asm volatile("" : "+a"(qf[c][kh][qt]));
-  float sq[QT], oaq[QT], aq[QT], bq[QT], sdq[QT];
-  uint32_t qcnt[QT];
-#pragma unroll
-  for (int qt = 0; qt < QT; ++qt) {
-    const int qq = qt * 16 + j;
-    const float4 v = qsc[qq];
-    sq[qt] = v.x;
-    aq[qt] = v.y;
-    oaq[qt] = 1.0f - v.y;
-    bq[qt] = v.z;
-    sdq[qt] = qq < nq ? seed[qq] : -__builtin_inff();
-    qcnt[qt] = 0u;
-  }
   i32x4q acc[4][QT];
 #pragma unroll
   for (int rt = 0; rt < 4; ++rt)
@@ -1220,6 +1279,7 @@ constexpr int kWideOvf = 64;    // overflowed (group, query) buffers one query m
 __global__ void __launch_bounds__(kWideThreads) dense_rerank_wide_kernel(
     const uint64_t *__restrict__ keys, const uint32_t *__restrict__ cnts, int n_wg, int qs, int k, int nq,
     const float *__restrict__ C, int ld, int dim, const float *__restrict__ q, const float4 *__restrict__ qsc,
+    const float *__restrict__ qbase,
     const _Float16 *__restrict__ Xh, const _Float16 *__restrict__ Qh, const float *__restrict__ qnorm,
     const float *__restrict__ row_norms, const int8_t *__restrict__ Xq, const float2 *__restrict__ rmeta,
     const int8_t *__restrict__ Qq, const uint32_t *__restrict__ live, const uint32_t *__restrict__ allow,
@@ -1303,11 +1363,12 @@ __global__ void __launch_bounds__(kWideThreads) dense_rerank_wide_kernel(
     }
   }
   // no full f16 plane (xh_rows_for): the overflowed groups' live & allowed rows are filtered on the
-  // int8 plane with the scan's own per-row bound, lo_r = 1 - a_q - b_q e_r - s_q S_r acc_r <= kth_up
+  // int8 plane with the scan's own per-row bound, lo_r = base_q - a_q - b_q e_r - s_q S_r acc_r <= kth_up
   // (acc_r exact in int32); one wave per row, lane l < 48 its 16-B piece (chunk l / 8, k-half (l / 4) % 2,
   // lane group l % 4) of the row and of the query fragment, sdot4 products, a 64-lane xor tree
   if (novf > 0 && Xh == nullptr) {
     const float4 qs4 = qsc[qi];
+    const float qb = qbase[qi];   // base_q
     const int64_t qt = qi >> 4;
     const int jq = qi & 15;
     const int c = lane >> 3, kh = (lane >> 2) & 1, gq = lane & 3;
@@ -1331,7 +1392,7 @@ __global__ void __launch_bounds__(kWideThreads) dense_rerank_wide_kernel(
         }
         for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
         const float2 m = rmeta[row];
-        const float lo = fmaf(-(qs4.x * m.x), (float)acc, fmaf(-qs4.z, m.y, 1.0f - qs4.y));
+        const float lo = fmaf(-(qs4.x * m.x), (float)acc, fmaf(-qs4.z, m.y, qb - qs4.y));
         if (lane == 0 && f32_order(lo) <= tkey) {
           const int p = atomicAdd(&s_n, 1);
           if (p < kWideCap) rows[p] = (uint32_t)row;

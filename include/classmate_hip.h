@@ -107,8 +107,32 @@ int cm_dense_compact(cm_dense *h, int64_t expect_live, int32_t shrink, int64_t *
  * re-quantised) and size becomes new_size.  new_size > size (or < 0) -> CM_EINVAL.  The last step of
  * cm_dense_compact, and of a sharded compaction on every shard.  No reference counterpart. */
 int cm_dense_truncate(cm_dense *h, int64_t new_size);
-/* ChromaVectorStore.reset_collection (vector_chroma.py:262-269). */
+/* ChromaVectorStore.reset_collection (vector_chroma.py:262-269).  Also clears the int8 plane's centre
+ * (cm_dense_set_center): a reset store is a never-written one. */
 int cm_dense_reset(cm_dense *h);
+/* Centre of the int8 coarse plane (K1q / K1q-s), for anisotropic embeddings (E5-like: every vector
+ * near one dominant direction, pairwise cosine 0.7-0.9).  With a centre mu the plane stores
+ * q8(xn - mu) and the constant mu.qn is added back exactly per query, so the per-row bound E_r shrinks
+ * with ||xn - mu|| while every result stays exact: the f16 plane, the seed and the fp64 re-rank read
+ * uncentred data, and results do not depend on mu (only the re-ranked band and the fallbacks do).
+ * mu: host array of dim floats, or NULL to clear the centre (the default: the plain plane, bit for
+ * bit).  A non-finite entry or ||mu||_2 > 1 -> CM_EINVAL with the handle as it was (a mean of unit
+ * vectors never exceeds 1).  Stores mu and re-quantises every written row group on the handle's
+ * stream; returns when done; no search or upsert may run concurrently.  On an empty store it only
+ * stores mu; later upserts, growth, cm_dense_compact and cm_dense_truncate quantise under it, and
+ * cm_dense_compact's shrink keeps it.  Where the automatic kinds are K1c / K1s (other dims,
+ * CM_DENSE_Q8=0) the centre is stored and changes no search.  No reference counterpart. */
+int cm_dense_set_center(cm_dense *h, const float *mu);
+/* The centre: mu_out (nullable, dim floats; zeros when none is set), *is_set (nullable) 1 or 0. */
+int cm_dense_get_center(cm_dense *h, float *mu_out, int32_t *is_set);
+/* Mean of the normalised live rows of [0, size), the natural centre: column sums of xn = c * invc in
+ * fp64 on the device (one pass over the fp32 rows, fixed reduction order: two calls on the same store
+ * return the same bits), divided by the live count and rounded to fp32.  mean_out: dim floats;
+ * *n_live_out nullable.  No live row -> zeros.  Waits for the device's pending work. */
+int cm_dense_mean(cm_dense *h, float *mean_out, int64_t *n_live_out);
+/* cm_dense_mean's fp64 column sums (dim doubles) and live count, undivided: what a sharded index adds
+ * across its shards before dividing once. */
+int cm_dense_column_sums(cm_dense *h, double *sums_out, int64_t *n_live_out);
 /* ChromaVectorStore.count (vector_chroma.py:255-260). */
 int64_t cm_dense_live_count(cm_dense *h);
 int64_t cm_dense_size(cm_dense *h); /* high-water row count */
