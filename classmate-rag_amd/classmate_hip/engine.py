@@ -319,7 +319,9 @@ class DenseIndex:
     def set_path(self, kind: int):
         """Force the scan kernel (0 auto, 1 fp32 K1, 3 K1c coarse + re-rank, 4 K1s <= 32-query f16
         streams, 5 K1q int8 resident passes, 6 K1q-s <= 32-query int8 streams -- the coarse kinds with
-        the certified re-rank; 2 = the retired K1b, automatic)."""
+        the certified re-rank; 2 = the retired K1b, automatic).  A store of dim 897-1024 (row stride
+        1024) runs kind 6 at every batch size, one stream pass per 32 queries; there every forced kind
+        but 1 maps to 6."""
         L.check(L.fn["cm_dense_set_path"](self._h, int(kind)), "cm_dense_set_path")
 
     def search_kind(self, nq: int, k: int) -> int:

@@ -1332,7 +1332,9 @@ DenseWs dense_ws_layout(const cm_dense *h, const DenseCfg &c, int k, void *base)
 // re-rank's middle stage reads the band rows' fp32 data directly (dense_rerank_q8_kernel with Xh =
 // nullptr: every band row gets its exact fp64 distance), and the K1c / K1s scans, which read every
 // row of the plane, are not eligible (dense_kind).  CM_DENSE_F16=full keeps the whole plane,
-// =prefix forces the prefix at any size (tests).
+// =prefix forces the prefix at any size (tests).  An ld 1024 store holds the prefix at every size and
+// under either setting: its only f16 reader is the seed sample (K1s <16, 1, MINONLY>); no f16 scan
+// and no f16 band stage has a 1024 instance.
 constexpr int64_t kXhFullRows = 4ll << 20;
 constexpr int64_t kXhPrefixFrac = 16;
 int xh_mode() {   // read at every allocation (a store's policy is fixed by its arrays, not re-read per search)
@@ -1343,11 +1345,14 @@ int xh_mode() {   // read at every allocation (a store's policy is fixed by its 
 }
 int64_t xh_rows_for(const cm_dense *h, int64_t cap) {
   const int m = xh_mode();
-  if (h->ld != 768 || m == 1 || (m == 0 && cap <= kXhFullRows)) return cap;
+  if (h->ld != 1024 && (h->ld != 768 || m == 1 || (m == 0 && cap <= kXhFullRows))) return cap;
   return std::min<int64_t>(cap, round_up(ceil_div(cap, kXhPrefixFrac), kStepRows));
 }
-// true when the f16 plane holds every written row (the K1c / K1s scans and the f16 band stage)
-bool xh_full(const cm_dense *h) { return round_up(std::max<int64_t>(h->size, 1), kStepRows) <= h->xh_rows; }
+// true when the f16 plane holds every written row (the K1c / K1s scans and the f16 band stage); never
+// at ld 1024, whose prefix may cover a store far below its capacity but has no such reader
+bool xh_full(const cm_dense *h) {
+  return h->ld != 1024 && round_up(std::max<int64_t>(h->size, 1), kStepRows) <= h->xh_rows;
+}
 
 // Bytes of the row arrays at `rows` rows (C fp32, invc, live bits, Xh f16 plane, Xq int8 plane + rmeta).
 int64_t dense_row_bytes(const cm_dense *h, int64_t rows) {
@@ -1550,10 +1555,11 @@ int dense_grow(cm_dense *h, int64_t need_rows) {
 
 // Scan kernel for (nq, k), the "search kind":
 //   CM_DENSE_Q8S   (K1q-s) dim-768, nq <= kSQ: per-wave HBM streams of the int8 plane + re-rank;
+//                          ld 1024 (dims 897-1024) at every nq, one stream pass per kSQ queries;
 //   CM_DENSE_Q8    (K1q)   dim-768 batches nq > kSQ: int8 plane, 256-query resident passes + re-rank;
 //   CM_DENSE_STREAM (K1s)  nq <= kSQ queries, other dims (384) or CM_DENSE_Q8=0: f16 plane streams;
 //   CM_DENSE_COARSE (K1c)  larger batches at dim 384 (or CM_DENSE_Q8=0): f16 resident passes;
-//   CM_DENSE_F32   (K1)    exact fp32 scan: k > 32, dims other than 384 / 768, corpora under
+//   CM_DENSE_F32   (K1)    exact fp32 scan: k > 32, strides other than 384 / 768 / 1024, corpora under
 //                          16384 rows (and the certificate's fallback).
 // CM_DENSE_PATH=f32|coarse|stream|q8|q8s (or cm_dense_set_path) forces a kind for A/B probes; an
 // ineligible forced kind falls back to the automatic rule.  The retired K1b (f16x3 split planes,
@@ -1572,9 +1578,12 @@ int dense_kind(const cm_dense *h, int nq, int k) {
   }();
   const int force = h->path ? h->path : env_force;
   // coarse scans: resident-query instances for ld 768 / 384, a sample of >= 1024 rows for the seed
-  const bool coarse_ok = k <= kBMaxK && (h->ld == 768 || h->ld == 384) && h->size >= 16384;
+  const bool coarse_ok = k <= kBMaxK && (h->ld == 768 || h->ld == 384 || h->ld == 1024) && h->size >= 16384;
   const bool q8_ok = coarse_ok && h->ld == 768;  // K1q / K1q-s: the 6-chunk (ld 768) instances
   if (force == CM_DENSE_F32 || !coarse_ok) return CM_DENSE_F32;
+  // ld 1024 (dims 897-1024): the 8-chunk K1q-s at every batch size, in passes of kSQ queries
+  // (coarse_config); every other forced kind has no 1024 instance and maps to it
+  if (h->ld == 1024) return CM_DENSE_Q8S;
   if (!xh_full(h)) {   // the f16 plane holds only the seed-sample prefix: the int8 scans (xh_rows_for)
     if (force == CM_DENSE_Q8) return CM_DENSE_Q8;
     return nq <= kSQ ? CM_DENSE_Q8S : CM_DENSE_Q8;
@@ -1628,7 +1637,9 @@ CoarseCfg coarse_config(const cm_dense *h, int nq, int kind) {
   c.q8s = kind == CM_DENSE_Q8S;
   c.q8 = kind == CM_DENSE_Q8 || c.q8s;                                    // int8 buffers + re-rank
   c.qs = stream ? kSQ : kBQPass;
-  c.n_pass = stream ? 1 : (int)ceil_div(nq, kBQPass);
+  // ld 1024 has no resident-query batched scan: a batch above kSQ queries streams the int8 plane once
+  // per kSQ queries, the passes side by side in the [pass][group][qs] buffer layout
+  c.n_pass = stream ? (h->ld == 1024 ? (int)ceil_div(nq, kSQ) : 1) : (int)ceil_div(nq, kBQPass);
   c.rows_end = round_up(std::max<int64_t>(h->size, 1), kStepRows);
   // row groups per pass: one pass fills the CUs; many passes (nq > 256) keep >= kMinGroups groups each
   // (more workgroups than CUs) -- fewer, longer groups would overflow the 128-slot (group, query)
@@ -1717,7 +1728,8 @@ int set_coarse_attrs() {
         {reinterpret_cast<const void *>(&dense_rerank_kernel), kGatherCap * 12},
         {reinterpret_cast<const void *>(&dense_q8_scan_kernel<>), kQLds},
         {reinterpret_cast<const void *>(&dense_q8_scan_kernel<K1Q_LDS_SHARED>), kQLdsShared},
-        {reinterpret_cast<const void *>(&dense_rerank_q8_kernel), kQRerankLds}};
+        {reinterpret_cast<const void *>(&dense_rerank_q8_kernel<768>), kQRerankLds},
+        {reinterpret_cast<const void *>(&dense_rerank_q8_kernel<1024>), kQRerankLds}};
     for (const auto &f : fs) {
       const hipError_t e = hipFuncSetAttribute(f.first, hipFuncAttributeMaxDynamicSharedMemorySize, f.second);
       if (e != hipSuccess) err = e;
@@ -1732,6 +1744,9 @@ using StreamFn = void (*)(const _Float16 *, const uint32_t *, const uint32_t *, 
                           const float *, int64_t, int64_t, int, int, uint64_t *, uint32_t *, float *);
 StreamFn stream_kernel(int ld, int nq, bool minonly) {
   const bool two = nq > 16;
+  // ld 1024: the seed sample alone, 16 queries per launch (two q-tiles would need 256 registers for the
+  // query fragments alone); launch_coarse gives a 17-32 query pass two launches
+  if (ld == 1024) return minonly && !two ? &dense_stream_scan_kernel<16, 1, true> : nullptr;
   if (ld == 768)
     return two ? (minonly ? &dense_stream_scan_kernel<12, 2, true> : &dense_stream_scan_kernel<12, 2, false>)
                : (minonly ? &dense_stream_scan_kernel<12, 1, true> : &dense_stream_scan_kernel<12, 1, false>);
@@ -1754,8 +1769,17 @@ Q8Fn q8_kernel(bool full, size_t &lds) {   // K1q: the full or the shared LDS fo
   lds = full ? kQLds : kQLdsShared;
   return full ? &dense_q8_scan_kernel<> : &dense_q8_scan_kernel<K1Q_LDS_SHARED>;
 }
-Q8Fn q8_stream_kernel(int nq) {   // K1q-s: one or two q-tiles
-  return nq > 16 ? &dense_q8_stream_kernel<2, K1QS_RING> : &dense_q8_stream_kernel<1, K1QS_RING>;
+Q8Fn q8_stream_kernel(int ld, int nq) {   // K1q-s: one or two q-tiles, 6 or 8 chunks per tile
+  if (ld == 1024)
+    return nq > 16 ? &dense_q8_stream_kernel<2, K1QS_RING8, 8> : &dense_q8_stream_kernel<1, K1QS_RING8, 8>;
+  return nq > 16 ? &dense_q8_stream_kernel<2, K1QS_RING, 6> : &dense_q8_stream_kernel<1, K1QS_RING, 6>;
+}
+// K1q's certificate + re-rank and its wide re-rank, by row stride
+using RerankQ8Fn = decltype(&dense_rerank_q8_kernel<768>);
+using RerankWideFn = decltype(&dense_rerank_wide_kernel<768>);
+RerankQ8Fn rerank_q8_kernel(int ld) { return ld == 1024 ? &dense_rerank_q8_kernel<1024> : &dense_rerank_q8_kernel<768>; }
+RerankWideFn rerank_wide_kernel(int ld) {
+  return ld == 1024 ? &dense_rerank_wide_kernel<1024> : &dense_rerank_wide_kernel<768>;
 }
 
 // The coarse kinds: prep -> sample pre-pass -> seed -> scan -> certificate + re-rank; the queries
@@ -1786,9 +1810,20 @@ int launch_coarse(cm_dense *h, const float *q_dev, int nq, int k, int kind, cons
   }
   // 2. sample pre-pass over the f16 plane's sample prefix (per-group minima): K1s or K1c, MINONLY
   if (c.stream) {
-    hipLaunchKernelGGL(stream_kernel(h->ld, nq, true), dim3((unsigned)ceil_div(c.n_wg_sample, 4)), dim3(256), 0, st,
-                       h->Xh, h->live, allow, n_words, w.qh, nq, (const float *)nullptr, c.rows_per_wg_sample,
-                       c.rows_end_sample, c.n_wg_sample, c.qs, (uint64_t *)nullptr, (uint32_t *)nullptr, w.mins);
+    // one launch per pass (ld 768: the one pass); ld 1024: one per 16 queries of every pass, on the
+    // pass's and the half's offsets into Qh and mins [pass][sample group][qs]
+    const int per = h->ld == 1024 ? 16 : c.qs;
+    for (int p = 0; p < c.n_pass; ++p) {
+      const int nqp = std::min(nq - p * c.qs, c.qs);
+      for (int q0 = 0; q0 < nqp; q0 += per) {
+        const StreamFn fn = stream_kernel(h->ld, std::min(nqp - q0, per), true);
+        if (!fn) CM_FAIL(CM_EUNSUPPORTED, "no f16 stream instance for this stride");
+        hipLaunchKernelGGL(fn, dim3((unsigned)ceil_div(c.n_wg_sample, 4)), dim3(256), 0, st, h->Xh, h->live, allow,
+                           n_words, w.qh + ((size_t)p * c.qs + q0) * h->ld, nqp - q0, (const float *)nullptr,
+                           c.rows_per_wg_sample, c.rows_end_sample, c.n_wg_sample, c.qs, (uint64_t *)nullptr,
+                           (uint32_t *)nullptr, w.mins + (size_t)p * c.n_wg_sample * c.qs + q0);
+      }
+    }
   } else {
     const CoarseFn fn = coarse_kernel(h->ld, true, lds);
     hipLaunchKernelGGL(fn, dim3((unsigned)((int64_t)c.n_pass * c.n_wg_sample)), dim3(256), lds, st, h->Xh, h->live,
@@ -1804,9 +1839,16 @@ int launch_coarse(cm_dense *h, const float *q_dev, int nq, int k, int kind, cons
   // 4. scan: rows under the seed -> candidate buffers
   h->timer.begin(st);
   if (c.q8s) {
-    hipLaunchKernelGGL(q8_stream_kernel(nq), dim3((unsigned)ceil_div(c.n_wg, 4)), dim3(256), 0, st, h->Xq, h->rmeta,
-                       h->live, allow, n_words, w.qq, w.qsc, (const float *)w.qbase, nq, (const float *)w.seed, c.rows_per_wg,
-                       c.rows_end, c.n_wg, w.keys, w.ups, w.cnt);
+    // one launch per pass of kSQ queries (ld 768: the one pass), on the pass's offsets: its query
+    // fragments (two 16-query tiles of ld x 16 bytes), constants, seeds and [pass][group][qs] buffers
+    for (int p = 0; p < c.n_pass; ++p) {
+      const int nqp = std::min(nq - p * c.qs, c.qs);
+      const size_t q0 = (size_t)p * c.qs, b0 = (size_t)p * c.n_wg * c.qs;
+      hipLaunchKernelGGL(q8_stream_kernel(h->ld, nqp), dim3((unsigned)ceil_div(c.n_wg, 4)), dim3(256), 0, st, h->Xq,
+                         h->rmeta, h->live, allow, n_words, w.qq + q0 * h->ld, w.qsc + q0, (const float *)w.qbase + q0,
+                         nqp, (const float *)w.seed + q0, c.rows_per_wg, c.rows_end, c.n_wg, w.keys + b0 * kQCap,
+                         w.ups + b0 * kQCap, w.cnt + b0);
+    }
   } else if (c.q8) {
     // deferred search (!run_exact): the caller runs other work beside it -> the shared LDS footprint
     // (CM_K1Q_SHARED_LDS=0: the full one, A/B)
@@ -1829,7 +1871,7 @@ int launch_coarse(cm_dense *h, const float *q_dev, int nq, int k, int kind, cons
   // 5. certificate + exact re-rank (failures -> fb_mask)
   if (c.q8) {
     const bool pilot = env_knob("CM_K1Q_PILOT", true);   // 0: the int8 band from kth_up alone (A/B)
-    hipLaunchKernelGGL(dense_rerank_q8_kernel, dim3(nq), dim3(kQRT), kQRerankLds, st, w.keys, w.ups, w.cnt, c.n_wg,
+    hipLaunchKernelGGL(rerank_q8_kernel(h->ld), dim3(nq), dim3(kQRT), kQRerankLds, st, w.keys, w.ups, w.cnt, c.n_wg,
                        c.qs, k, nq, h->C, h->ld, h->dim, q_dev, w.qsc, xh_full(h) ? h->Xh : nullptr, w.qh, w.qnorm,
                        h->rnorm, dist_dev, row_dev, w.fb_mask, w.fb_count, w.fb_bound,
                        pilot ? 1 : 0, reinterpret_cast<unsigned long long *>(w.wide_ctr + 2));
@@ -1837,7 +1879,7 @@ int launch_coarse(cm_dense *h, const float *q_dev, int nq, int k, int kind, cons
     // band overflow with complete candidate buffers: the wide re-rank (gated; ~5 us when none failed;
     // CM_K1Q_WIDE=0: the exact scan takes every failing query, A/B)
     if (env_knob("CM_K1Q_WIDE", true))
-      hipLaunchKernelGGL(dense_rerank_wide_kernel, dim3(nq), dim3(kWideThreads), 0, st, w.keys, w.cnt, c.n_wg, c.qs,
+      hipLaunchKernelGGL(rerank_wide_kernel(h->ld), dim3(nq), dim3(kWideThreads), 0, st, w.keys, w.cnt, c.n_wg, c.qs,
                          k, nq, h->C, h->ld, h->dim, q_dev, w.qsc, (const float *)w.qbase,
                          xh_full(h) ? h->Xh : nullptr, w.qh, w.qnorm, h->rnorm, h->Xq, h->rmeta, w.qq, h->live, allow, n_words, c.rows_per_wg, c.rows_end, dist_dev,
                          row_dev, w.fb_mask, w.fb_count, w.fb_bound, w.wide_ctr, w.wide_rows, w.wide_keys);

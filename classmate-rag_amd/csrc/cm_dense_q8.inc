@@ -19,6 +19,25 @@
 // ~4,000; tools/int8_band.py, profiles/r04_int8_band_rowE.json); with the group scales below it is
 // 1,190 rows from kth_up alone and 200 with the re-rank's pilot bound (profiles/rerank_pilot.txt).
 //
+//
+// The slack by row stride n = ld (768, and 1024 for dims 897-1024), u = 2^-24.  What depends on n:
+//   the norms.  invc and the query's inv come from an fp32 sum of squares -- per thread a chain of
+//     n / 256 terms (3, 4), then 6 shuffle steps and 2 adds -- so the sum carries <= (n / 256 + 8) u
+//     relative, its square root half of that, and sqrtf, the + 1e-30 and the reciprocal <= u each: the
+//     common factor of xn (qn) against the fp64 normalisation is off by <= ((n / 256 + 8) / 2 + 3) u
+//     = 8.5 u (9 u), and each component's product rounding adds u by Cauchy-Schwarz.  Both operands:
+//     |xn.qn - x^.q^| <= 19 u = 1.13e-6 (20 u = 1.19e-6);
+//   acc.  |acc| <= 127^2 n = 12 387 072 (16 516 096) < 2^24, so (float)acc is exact at both strides
+//     (it stops being so at n = 1152: a stride above 1024 needs a split or an int bound instead);
+//   the fp64 sums of e_r, e_q, ||qn||, m_q and of the re-rank carry n 2^-53 <= 1.2e-13 relative, far
+//     inside the (1 + 1e-6) factors they are rounded up by.
+//   What does not: A = fl32(s_q S) (u on |A acc| <= 1.02), the fma of lo (u: |lo| < 2), the two
+//     roundings of B (u together, B < 1), a_q + b_q e_r (under u), the returned float (u, see
+//     kQPilotPad): <= 4.1 u = 2.5e-7; W's own 1e-6 covers lo + W and the factor 2.
+//   Sum: 1.38e-6 at 768, 1.44e-6 at 1024 -- one u more for the longer chains -- against 4e-6.  The
+//   constants (4e-6, the centre's 5e-7, W's 1e-6) are therefore the same at both strides, and every
+//   768 value keeps its bits.
+//
 // Centred plane (cm_dense_set_center).  Embedding models such as E5 put every vector near one
 // dominant direction (pairwise cosine 0.7-0.9): the distances around the k-th best then spread
 // several times less than on isotropic rows while e_r stays what it was, and the band grows until
@@ -40,7 +59,7 @@
 //     <= 2^-24 * 2 * (1 + 1e-6)                                                   < 1.2e-7;
 //   m_q: the term qn-against-the-fp64-normalisation is the plain plane's xn.(q^ - qn), already in the
 //     4e-6 (xn.q^ = xn.(q^ - qn) + y.qn + mu.qn + ...: mu multiplies the same fp32 qn the codes were
-//     made from), so only the fp64 sum's own rounding is new: <= 768 * 2^-53 * ||mu|| ||qn||  < 1e-13;
+//     made from), so only the fp64 sum's own rounding is new: <= ld * 2^-53 * ||mu|| ||qn||  < 1.2e-13;
 //   base_q = fl32(1 - m_q), |1 - m_q| <= 2 + 1e-6:                  <= 2^-24 * 2.01  < 1.2e-7;
 //   base_q - a_q and B = base_q - a_q - b_q E now reach 2 where 1 - a_q stayed below 1: each of the
 //     two fp32 roundings can double, + 2 * 2^-24                                  < 1.2e-7.
@@ -682,14 +701,35 @@ __global__ void __launch_bounds__(256, 1)
 // acc); the few passing lanes test their rows and append (f32_order(lo), row) and up = lo + W to
 // the (vg, query) buffer, slots from the running count all four lanes g of query j keep (a prefix
 // of the lanes' hit counts, no atomics).  The tile's rmeta, live and allow words are loaded at the
-// top of the tile and consumed by its epilogue six chunks later.  Output layout = K1q's with one
+// top of the tile and consumed by its epilogue KC chunks later.  Output layout = K1q's with one
 // pass of kSQ queries and n_wg = n_vg, so dense_rerank_q8_kernel certifies and re-ranks it
 // unchanged (the same keys, bounds and fp64 distances as the batched K1q).
+//
+// KC = 128-k chunks per 64-row tile: 6 (ld 768) or 8 (ld 1024, dims 897-1024).  At ld 1024 this kernel
+// is the scan of every batch size: a batch above kSQ queries is launched once per kSQ queries on the
+// pass's offsets into the fragments, constants, seeds and [pass][group][qs] buffers (launch_coarse),
+// so it streams the plane once per pass; a resident-query batched scan would need all 256 AGPRs for
+// 256 queries' fragments (KC x 2 x 4 x 4 x 2).  Registers at KC = 8: query fragments KC x 2 x QT x 4 =
+// 64 QT AGPRs, accumulators 16 QT, the ring 32 R, the tile's metadata 34.  Resource report (gfx950,
+// one wave per SIMD, no scratch in any of them):
+//     <QT, R, KC>   VGPRs  AGPRs            <QT, R, KC>   VGPRs  AGPRs
+//     <1, 4, 6>      254     48             <2, 4, 6>      256    107     (the ld 768 product)
+//     <1, 4, 8>      256     65             <2, 4, 8>      256    155
+//     <1, 3, 8>      198     64             <2, 3, 8>      214    128
+//     <1, 2, 8>      168     64 (2 waves)   <2, 2, 8>      208    128
+// R = 4 for both KC = 8 instances (K1QS_RING8), as at KC = 6: three chunks = 24 KiB per wave, 96 KiB
+// per CU in flight, against 64 KiB at R = 3 -- 8 TB/s x ~2 us over 256 CUs wants ~64 KiB per CU, so
+// R = 3 has no margin; R = 4 divides KC (TU = 1: one tile of code, where R = 3 unrolls three) and the
+// AGPRs above the fragments' 64 QT (1 and 27) are values the allocator parks there instead of
+// spilling, as the KC = 6 product does (11 at QT = 2).
 #ifndef K1QS_RING
 #define K1QS_RING 4
 #endif
+#ifndef K1QS_RING8
+#define K1QS_RING8 4
+#endif
 constexpr int cgcd(int a, int b) { return b == 0 ? a : cgcd(b, a % b); }
-template <int QT, int R>
+template <int QT, int R, int KC>
 __global__ void __launch_bounds__(256, 1)
     dense_q8_stream_kernel(const int8_t *__restrict__ Xq, const float2 *__restrict__ rmeta,
                            const uint32_t *__restrict__ live, const uint32_t *__restrict__ allow, int64_t n_words,
@@ -698,7 +738,7 @@ __global__ void __launch_bounds__(256, 1)
                            const float *__restrict__ seed, int64_t rows_per_vg, int64_t rows_end, int n_vg,
                            uint64_t *__restrict__ out_keys, float *__restrict__ out_up,
                            uint32_t *__restrict__ out_cnt) {
-  constexpr int KC = 6;                     // 128-k chunks per 64-row tile at ld 768
+  static_assert(KC == 6 || KC == 8, "K1q-s: 128-k chunks per 64-row tile, ld 768 or 1024");
   constexpr int TU = R / cgcd(R, KC);       // tiles per unrolled iteration: static ring slots
   const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -958,12 +998,12 @@ constexpr uint64_t kQTaken = ~0ull;   // a gathered candidate the pilot scored (
 // (f32_order(distance), row) to out[c].  out may be src (the pilot): entry c is read and written by
 // one wave, in that order; the clamped read of entry n - 1 by another wave may see that entry's key
 // instead of its row, and a key's low word -- all that is read -- is the row.
-// ld = 768: 12 strided elements per lane, loaded unconditionally (rows are zero past dim, and so
-// is s_q: the extra terms add exact zeros, so the sums equal dense_rerank_kernel's over dim).
-template <int NR, typename R>
+// M = ld / 64 strided elements per lane (12 at ld 768, 16 at ld 1024), loaded unconditionally (rows
+// are zero past dim, and so is s_q: the extra terms add exact zeros, so the sums equal
+// dense_rerank_kernel's over dim).
+template <int NR, int M, typename R>
 __device__ __forceinline__ void q8_exact_rows(const R *src, int n, int c0, int stride, const float *__restrict__ C,
                                               int ld, const float *s_q, double qnrm, int lane, uint64_t *out) {
-  constexpr int M = 12;
   float x[NR][M];
   uint32_t rows[NR];
 #pragma unroll
@@ -1002,6 +1042,10 @@ __device__ __forceinline__ void q8_exact_rows(const R *src, int n, int c0, int s
   }
 }
 
+// LD = the store's row stride: 768, or 1024 -- whose stores keep only the f16 plane's sample prefix
+// (xh_rows_for), so that instance has no f16 stage, and ranks 6 rows per wave at a time in the fp64
+// stage instead of 8: 6 x 16 = the 96 row registers of 8 x 12 (16 waves leave 128 VGPRs per lane).
+template <int LD>
 __global__ void __launch_bounds__(kQRT) dense_rerank_q8_kernel(
     const uint64_t *__restrict__ keys, const float *__restrict__ ups, const uint32_t *__restrict__ cnts, int n_wg,
     int qs, int k, int nq, const float *__restrict__ C, int ld, int dim, const float *__restrict__ q,
@@ -1013,12 +1057,15 @@ __global__ void __launch_bounds__(kQRT) dense_rerank_q8_kernel(
   if (qi >= nq) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int qp = qi / qs, ql = qi - qp * qs;   // qs: queries per pass of the buffer layout (K1q 256, K1q-s 32)
+  static_assert(LD == 768 || LD == 1024, "K1q re-rank: row strides with an int8 scan");
+  constexpr int M = LD / 64, NR = LD == 768 ? kQRows : 6;   // elements per lane; fp64-stage rows per wave
+  constexpr bool kF16Stage = LD == 768;
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
   uint64_t *g_key = reinterpret_cast<uint64_t *>(dyn);                 // [kQGather]
   uint32_t *g_up = reinterpret_cast<uint32_t *>(dyn + kQGather * 8);   // [kQGather] f32_order(up)
   __shared__ uint32_t s_off[2049];
   __shared__ uint32_t hist[256];
-  __shared__ float s_q[768];
+  __shared__ float s_q[LD];
   __shared__ int s_flag, s_total, s_band;
   __shared__ uint64_t s_sel[kQSel];
   __shared__ int s_nsel;
@@ -1076,7 +1123,7 @@ __global__ void __launch_bounds__(kQRT) dense_rerank_q8_kernel(
       g_up[jj] = f32_order(ups[sl]);
     }
   }
-  for (int i = tid; i < 768; i += kQRT) s_q[i] = i < dim ? q[(int64_t)qi * dim + i] : 0.f;  // zero past dim
+  for (int i = tid; i < LD; i += kQRT) s_q[i] = i < dim ? q[(int64_t)qi * dim + i] : 0.f;  // zero past dim
   __syncthreads();
   auto key_at = [&](int jj) -> uint64_t { return gathered ? g_key[jj] : keys[slot_of(jj)]; };
   auto up_at = [&](int jj) -> uint32_t { return gathered ? g_up[jj] : f32_order(ups[slot_of(jj)]); };
@@ -1117,7 +1164,7 @@ __global__ void __launch_bounds__(kQRT) dense_rerank_q8_kernel(
       __syncthreads();
       // row c on wave c % kQRW: k + ties <= kQRW * kQPilotRows = 32 rows are one round of loads
       for (int c0 = wave; c0 < npilot; c0 += kQRW * kQPilotRows)
-        q8_exact_rows<kQPilotRows>(s_sel, npilot, c0, kQRW, C, ld, s_q, qnrm, lane, s_sel);
+        q8_exact_rows<kQPilotRows, M>(s_sel, npilot, c0, kQRW, C, ld, s_q, qnrm, lane, s_sel);
       __syncthreads();
       const uint32_t pkey = block_select_fn([&](int i) { return (uint32_t)(s_sel[i] >> 32); }, npilot, k - 1, hist);
       bound = min(tkey, pkey <= 0xffffffffu - kQPilotPad ? pkey + kQPilotPad : 0xffffffffu);
@@ -1151,7 +1198,7 @@ __global__ void __launch_bounds__(kQRT) dense_rerank_q8_kernel(
   }
   const uint32_t *band_rows = s_rows;   // the rows the fp64 stage re-ranks: the f16 band, or (no full
   int band2 = band;                     // f16 plane, xh_rows_for) the whole int8 band
-  if (Xh != nullptr) {
+  if (kF16Stage && Xh != nullptr) {
   // 5'. f16 middle stage (K1c's certificate): the band rows' coarse distances from the f16 plane,
   // d_h = 1 - xh . qh (fp32), |(1 - xn . qn) - d_h| <= Eh (coarse_err); kth_h = the k-th smallest
   // d_h + Eh over the band (>= the true k-th distance: the band holds every true top-k row), band2 =
@@ -1227,8 +1274,8 @@ __global__ void __launch_bounds__(kQRT) dense_rerank_q8_kernel(
   }
   }   // Xh != nullptr (without it: s_ex = g_key's 64 KiB holds kQBand keys beside s_rows in g_up's space)
   if (tid == 0) atomicAdd(band_ctr, (unsigned long long)(band2 + npilot));
-  for (int c0 = wave * kQRows; c0 < band2; c0 += kQRW * kQRows)
-    q8_exact_rows<kQRows>(band_rows, band2, c0, 1, C, ld, s_q, qnrm, lane, s_ex);
+  for (int c0 = wave * NR; c0 < band2; c0 += kQRW * NR)
+    q8_exact_rows<NR, M>(band_rows, band2, c0, 1, C, ld, s_q, qnrm, lane, s_ex);
   if (tid < npilot) s_ex[band2 + tid] = s_sel[tid];   // the pilot rows' keys join the band's
   band2 += npilot;
   __syncthreads();
@@ -1276,6 +1323,7 @@ constexpr int kWideSlots = 16;
 constexpr int kWideCap = 1 << 16;
 constexpr int kWideThreads = 1024;
 constexpr int kWideOvf = 64;    // overflowed (group, query) buffers one query may re-scan
+template <int LD>
 __global__ void __launch_bounds__(kWideThreads) dense_rerank_wide_kernel(
     const uint64_t *__restrict__ keys, const uint32_t *__restrict__ cnts, int n_wg, int qs, int k, int nq,
     const float *__restrict__ C, int ld, int dim, const float *__restrict__ q, const float4 *__restrict__ qsc,
@@ -1294,7 +1342,7 @@ __global__ void __launch_bounds__(kWideThreads) dense_rerank_wide_kernel(
   const int qp = qi / qs, ql = qi - qp * qs;
   __shared__ uint32_t s_off[2049];
   __shared__ uint32_t hist[256];
-  __shared__ float s_q[768];
+  __shared__ float s_q[LD];
   __shared__ uint64_t s_sel[kQSel];
   __shared__ int s_ovf[kWideOvf];
   __shared__ int s_slot, s_n, s_nsel, s_total, s_novf;
@@ -1337,7 +1385,7 @@ __global__ void __launch_bounds__(kWideThreads) dense_rerank_wide_kernel(
       s_total = (int)run;
     }
   }
-  for (int i = tid; i < 768; i += kWideThreads) s_q[i] = i < dim ? q[(int64_t)qi * dim + i] : 0.f;  // zero past dim
+  for (int i = tid; i < LD; i += kWideThreads) s_q[i] = i < dim ? q[(int64_t)qi * dim + i] : 0.f;  // zero past dim
   __syncthreads();
   const int slot = s_slot;
   const int novf = s_novf;
@@ -1364,7 +1412,7 @@ __global__ void __launch_bounds__(kWideThreads) dense_rerank_wide_kernel(
   }
   // no full f16 plane (xh_rows_for): the overflowed groups' live & allowed rows are filtered on the
   // int8 plane with the scan's own per-row bound, lo_r = base_q - a_q - b_q e_r - s_q S_r acc_r <= kth_up
-  // (acc_r exact in int32); one wave per row, lane l < 48 its 16-B piece (chunk l / 8, k-half (l / 4) % 2,
+  // (acc_r exact in int32); one wave per row, lane l < LD / 16 (48, or all 64) its 16-B piece (chunk l / 8, k-half (l / 4) % 2,
   // lane group l % 4) of the row and of the query fragment, sdot4 products, a 64-lane xor tree
   if (novf > 0 && Xh == nullptr) {
     const float4 qs4 = qsc[qi];
@@ -1373,7 +1421,7 @@ __global__ void __launch_bounds__(kWideThreads) dense_rerank_wide_kernel(
     const int jq = qi & 15;
     const int c = lane >> 3, kh = (lane >> 2) & 1, gq = lane & 3;
     i32x4q qv = {0, 0, 0, 0};
-    if (lane < 48)
+    if (lane < LD / 16)
       qv = *reinterpret_cast<const i32x4q *>(Qq + ((((qt * (ld >> 7) + c) * 2 + kh) << 10) + ((gq * 16 + jq) << 4)));
     for (int g = 0; g < novf; ++g) {
       const int64_t r0 = (int64_t)s_ovf[g] * rows_per_wg, r1 = min(r0 + rows_per_wg, rows_end);
@@ -1384,7 +1432,7 @@ __global__ void __launch_bounds__(kWideThreads) dense_rerank_wide_kernel(
         const int64_t tile = row >> 6;
         const int rr = (int)(row & 63), rt = rr >> 4, jj = rr & 15;
         int acc = 0;
-        if (lane < 48) {
+        if (lane < LD / 16) {
           const i32x4q xv = *reinterpret_cast<const i32x4q *>(
               Xq + ((((tile * (ld >> 7) + c) * 8 + rt * 2 + kh) << 10) + ((gq * 16 + jj) << 4)));
 #pragma unroll
@@ -1402,7 +1450,7 @@ __global__ void __launch_bounds__(kWideThreads) dense_rerank_wide_kernel(
   }
   // the overflowed groups' live & allowed rows, filtered on the f16 plane: d_h - Eh <= kth_up (the f16
   // stage of dense_rerank_q8_kernel: half a wave per row, its 16-B plane pieces l, l + 32, l + 64)
-  if (novf > 0 && Xh != nullptr) {
+  if (LD == 768 && novf > 0 && Xh != nullptr) {   // (an ld 1024 store never holds the full plane)
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     const float Eh = coarse_err(qnorm, qi, row_norms, dim);
     const int hl = lane & 31, hh = lane >> 5;
@@ -1445,9 +1493,9 @@ __global__ void __launch_bounds__(kWideThreads) dense_rerank_wide_kernel(
     if (tid == 0) fb_mask[qi] = 1;
     return;
   }
-  // exact fp64 distances, dense_rerank_q8_kernel's arithmetic (ld = 768: 12 strided elements per lane)
+  // exact fp64 distances, dense_rerank_q8_kernel's arithmetic (LD / 64 strided elements per lane)
   const double qnrm = (double)qsc[qi].w;
-  constexpr int M = 12, WR = 4;   // rows per wave and iteration (<= 128 VGPRs at 16 waves)
+  constexpr int M = LD / 64, WR = 4;   // rows per wave and iteration (<= 128 VGPRs at 16 waves)
   for (int c0 = wave * WR; c0 < n; c0 += NW * WR) {
     float x[WR][M];
     uint32_t rr[WR];
