@@ -321,7 +321,9 @@ class DenseIndex:
         streams, 5 K1q int8 resident passes, 6 K1q-s <= 32-query int8 streams -- the coarse kinds with
         the certified re-rank; 2 = the retired K1b, automatic).  A store of dim 897-1024 (row stride
         1024) runs kind 6 at every batch size, one stream pass per 32 queries; there every forced kind
-        but 1 maps to 6."""
+        but 1 maps to 6.  A store of dim 257-384 (row stride 384) runs kind 6 up to 32 queries and kind 3
+        above; a forced 6 is honoured there at every batch size (in passes), a forced 5 is not compiled
+        for that stride and falls to the automatic rule."""
         L.check(L.fn["cm_dense_set_path"](self._h, int(kind)), "cm_dense_set_path")
 
     def search_kind(self, nq: int, k: int) -> int:

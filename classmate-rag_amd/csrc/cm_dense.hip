@@ -1556,14 +1556,18 @@ int dense_grow(cm_dense *h, int64_t need_rows) {
 // Scan kernel for (nq, k), the "search kind":
 //   CM_DENSE_Q8S   (K1q-s) dim-768, nq <= kSQ: per-wave HBM streams of the int8 plane + re-rank;
 //                          ld 1024 (dims 897-1024) at every nq, one stream pass per kSQ queries;
+//                          ld 384 (dims 257-384) for nq <= kSQ, and at every nq when forced (in passes);
 //   CM_DENSE_Q8    (K1q)   dim-768 batches nq > kSQ: int8 plane, 256-query resident passes + re-rank;
-//   CM_DENSE_STREAM (K1s)  nq <= kSQ queries, other dims (384) or CM_DENSE_Q8=0: f16 plane streams;
-//   CM_DENSE_COARSE (K1c)  larger batches at dim 384 (or CM_DENSE_Q8=0): f16 resident passes;
+//   CM_DENSE_STREAM (K1s)  nq <= kSQ queries with CM_DENSE_Q8=0 (ld 768 / 384) or forced: f16 plane streams;
+//   CM_DENSE_COARSE (K1c)  larger batches at ld 384 (or CM_DENSE_Q8=0): f16 resident passes;
 //   CM_DENSE_F32   (K1)    exact fp32 scan: k > 32, strides other than 384 / 768 / 1024, corpora under
 //                          16384 rows (and the certificate's fallback).
 // CM_DENSE_PATH=f32|coarse|stream|q8|q8s (or cm_dense_set_path) forces a kind for A/B probes; an
 // ineligible forced kind falls back to the automatic rule.  The retired K1b (f16x3 split planes,
 // kind 2) maps to the automatic rule.
+// Strides whose K1q-s takes a batch above kSQ queries in passes of kSQ (coarse_config, launch_coarse):
+// they have no resident-query batched int8 scan (K1q is compiled for ld 768 alone).
+bool q8s_in_passes(int ld) { return ld == 1024 || ld == 384; }
 int dense_kind(const cm_dense *h, int nq, int k) {
   static const int env_force = [] {
     const char *e = getenv("CM_DENSE_PATH");
@@ -1580,6 +1584,9 @@ int dense_kind(const cm_dense *h, int nq, int k) {
   // coarse scans: resident-query instances for ld 768 / 384, a sample of >= 1024 rows for the seed
   const bool coarse_ok = k <= kBMaxK && (h->ld == 768 || h->ld == 384 || h->ld == 1024) && h->size >= 16384;
   const bool q8_ok = coarse_ok && h->ld == 768;  // K1q / K1q-s: the 6-chunk (ld 768) instances
+  // K1q-s alone also has the 3-chunk (ld 384) instances: automatic up to kSQ queries (two int8 passes
+  // already read the 768 B per row K1c reads once for 256 queries); forced, every batch size, in passes
+  const bool q8s_ok = q8_ok || (coarse_ok && h->ld == 384);
   if (force == CM_DENSE_F32 || !coarse_ok) return CM_DENSE_F32;
   // ld 1024 (dims 897-1024): the 8-chunk K1q-s at every batch size, in passes of kSQ queries
   // (coarse_config); every other forced kind has no 1024 instance and maps to it
@@ -1591,10 +1598,10 @@ int dense_kind(const cm_dense *h, int nq, int k) {
   if (force == CM_DENSE_COARSE) return CM_DENSE_COARSE;
   if (force == CM_DENSE_STREAM && nq <= kSQ) return CM_DENSE_STREAM;
   if (force == CM_DENSE_Q8 && q8_ok) return CM_DENSE_Q8;
-  if (force == CM_DENSE_Q8S && q8_ok && nq <= kSQ) return CM_DENSE_Q8S;
+  if (force == CM_DENSE_Q8S && q8s_ok && (nq <= kSQ || q8s_in_passes(h->ld))) return CM_DENSE_Q8S;
   // small batches: the int8 stream (half K1s's bytes; round 4 ran them on the batched K1q from 4M
   // rows, whose 256-slot MFMA work and LDS ring are waste at <= 32 queries)
-  if (nq <= kSQ) return (q8_ok && q8_auto) ? CM_DENSE_Q8S : CM_DENSE_STREAM;
+  if (nq <= kSQ) return (q8s_ok && q8_auto) ? CM_DENSE_Q8S : CM_DENSE_STREAM;
   return (q8_ok && q8_auto) ? CM_DENSE_Q8 : CM_DENSE_COARSE;
 }
 
@@ -1637,9 +1644,10 @@ CoarseCfg coarse_config(const cm_dense *h, int nq, int kind) {
   c.q8s = kind == CM_DENSE_Q8S;
   c.q8 = kind == CM_DENSE_Q8 || c.q8s;                                    // int8 buffers + re-rank
   c.qs = stream ? kSQ : kBQPass;
-  // ld 1024 has no resident-query batched scan: a batch above kSQ queries streams the int8 plane once
-  // per kSQ queries, the passes side by side in the [pass][group][qs] buffer layout
-  c.n_pass = stream ? (h->ld == 1024 ? (int)ceil_div(nq, kSQ) : 1) : (int)ceil_div(nq, kBQPass);
+  // a stride without a resident-query batched int8 scan (q8s_in_passes) streams the int8 plane once per
+  // kSQ queries, the passes side by side in the [pass][group][qs] buffer layout (K1s at such a stride
+  // only ever gets nq <= kSQ: one pass)
+  c.n_pass = stream ? (q8s_in_passes(h->ld) ? (int)ceil_div(nq, kSQ) : 1) : (int)ceil_div(nq, kBQPass);
   c.rows_end = round_up(std::max<int64_t>(h->size, 1), kStepRows);
   // row groups per pass: one pass fills the CUs; many passes (nq > 256) keep >= kMinGroups groups each
   // (more workgroups than CUs) -- fewer, longer groups would overflow the 128-slot (group, query)
@@ -1729,7 +1737,8 @@ int set_coarse_attrs() {
         {reinterpret_cast<const void *>(&dense_q8_scan_kernel<>), kQLds},
         {reinterpret_cast<const void *>(&dense_q8_scan_kernel<K1Q_LDS_SHARED>), kQLdsShared},
         {reinterpret_cast<const void *>(&dense_rerank_q8_kernel<768>), kQRerankLds},
-        {reinterpret_cast<const void *>(&dense_rerank_q8_kernel<1024>), kQRerankLds}};
+        {reinterpret_cast<const void *>(&dense_rerank_q8_kernel<1024>), kQRerankLds},
+        {reinterpret_cast<const void *>(&dense_rerank_q8_kernel<384>), kQRerankLds}};
     for (const auto &f : fs) {
       const hipError_t e = hipFuncSetAttribute(f.first, hipFuncAttributeMaxDynamicSharedMemorySize, f.second);
       if (e != hipSuccess) err = e;
@@ -1769,7 +1778,9 @@ Q8Fn q8_kernel(bool full, size_t &lds) {   // K1q: the full or the shared LDS fo
   lds = full ? kQLds : kQLdsShared;
   return full ? &dense_q8_scan_kernel<> : &dense_q8_scan_kernel<K1Q_LDS_SHARED>;
 }
-Q8Fn q8_stream_kernel(int ld, int nq) {   // K1q-s: one or two q-tiles, 6 or 8 chunks per tile
+Q8Fn q8_stream_kernel(int ld, int nq) {   // K1q-s: one or two q-tiles, 3, 6 or 8 chunks per tile
+  if (ld == 384)
+    return nq > 16 ? &dense_q8_stream_kernel<2, K1QS_RING3, 3> : &dense_q8_stream_kernel<1, K1QS_RING3, 3>;
   if (ld == 1024)
     return nq > 16 ? &dense_q8_stream_kernel<2, K1QS_RING8, 8> : &dense_q8_stream_kernel<1, K1QS_RING8, 8>;
   return nq > 16 ? &dense_q8_stream_kernel<2, K1QS_RING, 6> : &dense_q8_stream_kernel<1, K1QS_RING, 6>;
@@ -1777,9 +1788,12 @@ Q8Fn q8_stream_kernel(int ld, int nq) {   // K1q-s: one or two q-tiles, 6 or 8 c
 // K1q's certificate + re-rank and its wide re-rank, by row stride
 using RerankQ8Fn = decltype(&dense_rerank_q8_kernel<768>);
 using RerankWideFn = decltype(&dense_rerank_wide_kernel<768>);
-RerankQ8Fn rerank_q8_kernel(int ld) { return ld == 1024 ? &dense_rerank_q8_kernel<1024> : &dense_rerank_q8_kernel<768>; }
+RerankQ8Fn rerank_q8_kernel(int ld) {
+  return ld == 1024 ? &dense_rerank_q8_kernel<1024> : ld == 384 ? &dense_rerank_q8_kernel<384> : &dense_rerank_q8_kernel<768>;
+}
 RerankWideFn rerank_wide_kernel(int ld) {
-  return ld == 1024 ? &dense_rerank_wide_kernel<1024> : &dense_rerank_wide_kernel<768>;
+  return ld == 1024 ? &dense_rerank_wide_kernel<1024>
+       : ld == 384  ? &dense_rerank_wide_kernel<384> : &dense_rerank_wide_kernel<768>;
 }
 
 // The coarse kinds: prep -> sample pre-pass -> seed -> scan -> certificate + re-rank; the queries
@@ -1871,8 +1885,11 @@ int launch_coarse(cm_dense *h, const float *q_dev, int nq, int k, int kind, cons
   // 5. certificate + exact re-rank (failures -> fb_mask)
   if (c.q8) {
     const bool pilot = env_knob("CM_K1Q_PILOT", true);   // 0: the int8 band from kth_up alone (A/B)
+    // the f16 band stage and the wide re-rank's f16 filter are compiled for ld 768 alone: every other
+    // stride takes the int8 band straight to fp64 (ld 384 holds the whole plane, for K1c / K1s)
+    const _Float16 *xh_band = h->ld == 768 && xh_full(h) ? h->Xh : nullptr;
     hipLaunchKernelGGL(rerank_q8_kernel(h->ld), dim3(nq), dim3(kQRT), kQRerankLds, st, w.keys, w.ups, w.cnt, c.n_wg,
-                       c.qs, k, nq, h->C, h->ld, h->dim, q_dev, w.qsc, xh_full(h) ? h->Xh : nullptr, w.qh, w.qnorm,
+                       c.qs, k, nq, h->C, h->ld, h->dim, q_dev, w.qsc, xh_band, w.qh, w.qnorm,
                        h->rnorm, dist_dev, row_dev, w.fb_mask, w.fb_count, w.fb_bound,
                        pilot ? 1 : 0, reinterpret_cast<unsigned long long *>(w.wide_ctr + 2));
     CM_HIP(hipGetLastError());
@@ -1881,7 +1898,7 @@ int launch_coarse(cm_dense *h, const float *q_dev, int nq, int k, int kind, cons
     if (env_knob("CM_K1Q_WIDE", true))
       hipLaunchKernelGGL(rerank_wide_kernel(h->ld), dim3(nq), dim3(kWideThreads), 0, st, w.keys, w.cnt, c.n_wg, c.qs,
                          k, nq, h->C, h->ld, h->dim, q_dev, w.qsc, (const float *)w.qbase,
-                         xh_full(h) ? h->Xh : nullptr, w.qh, w.qnorm, h->rnorm, h->Xq, h->rmeta, w.qq, h->live, allow, n_words, c.rows_per_wg, c.rows_end, dist_dev,
+                         xh_band, w.qh, w.qnorm, h->rnorm, h->Xq, h->rmeta, w.qq, h->live, allow, n_words, c.rows_per_wg, c.rows_end, dist_dev,
                          row_dev, w.fb_mask, w.fb_count, w.fb_bound, w.wide_ctr, w.wide_rows, w.wide_keys);
   } else {
     hipLaunchKernelGGL(dense_rerank_kernel, dim3(nq), dim3(256), kGatherCap * 12, st, w.keys, w.cnt, c.n_wg, c.qs, k,

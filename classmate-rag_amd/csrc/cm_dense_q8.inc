@@ -20,23 +20,26 @@
 // 1,190 rows from kth_up alone and 200 with the re-rank's pilot bound (profiles/rerank_pilot.txt).
 //
 //
-// The slack by row stride n = ld (768, and 1024 for dims 897-1024), u = 2^-24.  What depends on n:
+// The slack by row stride n = ld (768; 1024 for dims 897-1024; 384 for dims 257-384), u = 2^-24.  What
+// depends on n, as 768 (1024; 384):
 //   the norms.  invc and the query's inv come from an fp32 sum of squares -- per thread a chain of
-//     n / 256 terms (3, 4), then 6 shuffle steps and 2 adds -- so the sum carries <= (n / 256 + 8) u
-//     relative, its square root half of that, and sqrtf, the + 1e-30 and the reciprocal <= u each: the
-//     common factor of xn (qn) against the fp64 normalisation is off by <= ((n / 256 + 8) / 2 + 3) u
-//     = 8.5 u (9 u), and each component's product rounding adds u by Cauchy-Schwarz.  Both operands:
-//     |xn.qn - x^.q^| <= 19 u = 1.13e-6 (20 u = 1.19e-6);
-//   acc.  |acc| <= 127^2 n = 12 387 072 (16 516 096) < 2^24, so (float)acc is exact at both strides
-//     (it stops being so at n = 1152: a stride above 1024 needs a split or an int bound instead);
-//   the fp64 sums of e_r, e_q, ||qn||, m_q and of the re-rank carry n 2^-53 <= 1.2e-13 relative, far
-//     inside the (1 + 1e-6) factors they are rounded up by.
+//     ceil(n / 256) terms (3, 4, 2), then 6 shuffle steps and 2 adds -- so the sum carries
+//     <= (ceil(n / 256) + 8) u relative, its square root half of that, and sqrtf, the + 1e-30 and the
+//     reciprocal <= u each: the common factor of xn (qn) against the fp64 normalisation is off by
+//     <= ((ceil(n / 256) + 8) / 2 + 3) u = 8.5 u (9 u; 8 u), and each component's product rounding adds
+//     u by Cauchy-Schwarz.  Both operands: |xn.qn - x^.q^| <= 19 u = 1.13e-6 (20 u = 1.19e-6; 18 u =
+//     1.07e-6);
+//   acc.  |acc| <= 127^2 n = 12 387 072 (16 516 096; 6 193 536) < 2^24, so (float)acc is exact at every
+//     stride (it stops being so at n = 1152: a stride above 1024 needs a split or an int bound instead);
+//   the fp64 sums of e_r, e_q, ||qn||, m_q and of the re-rank carry n 2^-53 <= 1.2e-13 relative
+//     (4.3e-14 at 384), far inside the (1 + 1e-6) factors they are rounded up by.
 //   What does not: A = fl32(s_q S) (u on |A acc| <= 1.02), the fma of lo (u: |lo| < 2), the two
 //     roundings of B (u together, B < 1), a_q + b_q e_r (under u), the returned float (u, see
 //     kQPilotPad): <= 4.1 u = 2.5e-7; W's own 1e-6 covers lo + W and the factor 2.
-//   Sum: 1.38e-6 at 768, 1.44e-6 at 1024 -- one u more for the longer chains -- against 4e-6.  The
-//   constants (4e-6, the centre's 5e-7, W's 1e-6) are therefore the same at both strides, and every
-//   768 value keeps its bits.
+//   Sum: 1.38e-6 at 768, 1.44e-6 at 1024 -- one u more for the longer chains --, 1.32e-6 at 384 -- one
+//   u less for the shorter ones -- against 4e-6.  The centre's terms (below) do not depend on n except
+//   m_q's fp64 sum, smaller at 384.  The constants (4e-6, the centre's 5e-7, W's 1e-6) are therefore
+//   the same at every stride, and every 768 and 1024 value keeps its bits.
 //
 // Centred plane (cm_dense_set_center).  Embedding models such as E5 put every vector near one
 // dominant direction (pairwise cosine 0.7-0.9): the distances around the k-th best then spread
@@ -705,7 +708,8 @@ __global__ void __launch_bounds__(256, 1)
 // pass of kSQ queries and n_wg = n_vg, so dense_rerank_q8_kernel certifies and re-ranks it
 // unchanged (the same keys, bounds and fp64 distances as the batched K1q).
 //
-// KC = 128-k chunks per 64-row tile: 6 (ld 768) or 8 (ld 1024, dims 897-1024).  At ld 1024 this kernel
+// KC = 128-k chunks per 64-row tile: 6 (ld 768), 8 (ld 1024, dims 897-1024) or 3 (ld 384, below).
+// At ld 1024 this kernel
 // is the scan of every batch size: a batch above kSQ queries is launched once per kSQ queries on the
 // pass's offsets into the fragments, constants, seeds and [pass][group][qs] buffers (launch_coarse),
 // so it streams the plane once per pass; a resident-query batched scan would need all 256 AGPRs for
@@ -722,11 +726,30 @@ __global__ void __launch_bounds__(256, 1)
 // R = 3 has no margin; R = 4 divides KC (TU = 1: one tile of code, where R = 3 unrolls three) and the
 // AGPRs above the fragments' 64 QT (1 and 27) are values the allocator parks there instead of
 // spilling, as the KC = 6 product does (11 at QT = 2).
+//
+// KC = 3 (ld 384, dims 257-384): the automatic scan up to kSQ queries, and in passes when forced
+// (dense_kind).  Query fragments 3 x 2 x QT x 4 = 24 QT AGPRs.  TU = R / gcd(R, 3), so the ring also
+// sets how many tiles of code are unrolled.  Candidates (no scratch, no LDS in any; in flight = R - 1
+// chunks of 8 KiB per wave, x 4 per CU):
+//     <QT, R, KC>   VGPRs  AGPRs  waves/SIMD    <QT, R, KC>   VGPRs  AGPRs    TU   in flight per wave
+//     <1, 3, 3>      184     24      2          <2, 3, 3>      212     48      1    16 KiB
+//     <1, 4, 3>      222     24      2          <2, 4, 3>      254     48      4    24 KiB
+//     <1, 6, 3>      256     47      1          <2, 6, 3>      256     99      2    40 KiB
+//     (<., 2, 3> 158 / 186 VGPRs and <., 5, 3> 256 + 77 / 123 AGPRs were compiled and not run)
+// Scan kernel alone at 1M x 384, k = 24, ms at 1 / 16 / 32 queries and two passes for 64
+// (profiles/dense_dim384.txt): R = 3 0.067 / 0.072 / 0.076 / 0.149, R = 4 0.067 / 0.073 / 0.078 / 0.154,
+// R = 6 0.067 / 0.073 / 0.081 / 0.156.  A deeper ring buys nothing here -- a tile is 24 KiB, so the 16 KiB
+// of R = 3 already cover two thirds of the next tile while this one's epilogue runs, and the stream is
+// shorter than at KC = 8, where R = 3 lost 6 % -- so K1QS_RING3 = 3: equal or ahead at every batch size,
+// one tile of code, the fewest registers.
 #ifndef K1QS_RING
 #define K1QS_RING 4
 #endif
 #ifndef K1QS_RING8
 #define K1QS_RING8 4
+#endif
+#ifndef K1QS_RING3
+#define K1QS_RING3 3
 #endif
 constexpr int cgcd(int a, int b) { return b == 0 ? a : cgcd(b, a % b); }
 template <int QT, int R, int KC>
@@ -738,7 +761,7 @@ __global__ void __launch_bounds__(256, 1)
                            const float *__restrict__ seed, int64_t rows_per_vg, int64_t rows_end, int n_vg,
                            uint64_t *__restrict__ out_keys, float *__restrict__ out_up,
                            uint32_t *__restrict__ out_cnt) {
-  static_assert(KC == 6 || KC == 8, "K1q-s: 128-k chunks per 64-row tile, ld 768 or 1024");
+  static_assert(KC == 3 || KC == 6 || KC == 8, "K1q-s: 128-k chunks per 64-row tile, ld 384, 768 or 1024");
   constexpr int TU = R / cgcd(R, KC);       // tiles per unrolled iteration: static ring slots
   const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -998,7 +1021,7 @@ constexpr uint64_t kQTaken = ~0ull;   // a gathered candidate the pilot scored (
 // (f32_order(distance), row) to out[c].  out may be src (the pilot): entry c is read and written by
 // one wave, in that order; the clamped read of entry n - 1 by another wave may see that entry's key
 // instead of its row, and a key's low word -- all that is read -- is the row.
-// M = ld / 64 strided elements per lane (12 at ld 768, 16 at ld 1024), loaded unconditionally (rows
+// M = ld / 64 strided elements per lane (12 at ld 768, 16 at ld 1024, 6 at ld 384), loaded unconditionally (rows
 // are zero past dim, and so is s_q: the extra terms add exact zeros, so the sums equal
 // dense_rerank_kernel's over dim).
 template <int NR, int M, typename R>
@@ -1045,6 +1068,10 @@ __device__ __forceinline__ void q8_exact_rows(const R *src, int n, int c0, int s
 // LD = the store's row stride: 768, or 1024 -- whose stores keep only the f16 plane's sample prefix
 // (xh_rows_for), so that instance has no f16 stage, and ranks 6 rows per wave at a time in the fp64
 // stage instead of 8: 6 x 16 = the 96 row registers of 8 x 12 (16 waves leave 128 VGPRs per lane).
+// LD = 384 (dims 257-384) holds the whole f16 plane, for K1c / K1s, but has no f16 stage either
+// (launch_coarse passes Xh = nullptr): the band goes straight to fp64 from the 1.5 KiB fp32 rows, 12
+// rows per wave at a time, 12 x 6 = 72 row registers -- 16 x 6 = 96 spills 3 registers beside the 64 of
+// the rows' fp64 sums (124 VGPRs at 12, 108 at 8, no scratch).
 template <int LD>
 __global__ void __launch_bounds__(kQRT) dense_rerank_q8_kernel(
     const uint64_t *__restrict__ keys, const float *__restrict__ ups, const uint32_t *__restrict__ cnts, int n_wg,
@@ -1057,8 +1084,9 @@ __global__ void __launch_bounds__(kQRT) dense_rerank_q8_kernel(
   if (qi >= nq) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int qp = qi / qs, ql = qi - qp * qs;   // qs: queries per pass of the buffer layout (K1q 256, K1q-s 32)
-  static_assert(LD == 768 || LD == 1024, "K1q re-rank: row strides with an int8 scan");
-  constexpr int M = LD / 64, NR = LD == 768 ? kQRows : 6;   // elements per lane; fp64-stage rows per wave
+  static_assert(LD == 384 || LD == 768 || LD == 1024, "K1q re-rank: row strides with an int8 scan");
+  // elements per lane; fp64-stage rows per wave
+  constexpr int M = LD / 64, NR = LD == 768 ? kQRows : LD == 1024 ? 6 : 12;
   constexpr bool kF16Stage = LD == 768;
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
   uint64_t *g_key = reinterpret_cast<uint64_t *>(dyn);                 // [kQGather]
@@ -1337,6 +1365,7 @@ __global__ void __launch_bounds__(kWideThreads) dense_rerank_wide_kernel(
     uint32_t *__restrict__ wide_rows, uint64_t *__restrict__ wide_keys) {
   const int qi = blockIdx.x;
   if (qi >= nq || *fb_count == 0 || fb_mask[qi] != 2) return;   // uniform per workgroup
+  static_assert(LD == 384 || LD == 768 || LD == 1024, "K1q wide re-rank: row strides with an int8 scan");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   constexpr int NW = kWideThreads / 64;
   const int qp = qi / qs, ql = qi - qp * qs;
@@ -1412,8 +1441,9 @@ __global__ void __launch_bounds__(kWideThreads) dense_rerank_wide_kernel(
   }
   // no full f16 plane (xh_rows_for): the overflowed groups' live & allowed rows are filtered on the
   // int8 plane with the scan's own per-row bound, lo_r = base_q - a_q - b_q e_r - s_q S_r acc_r <= kth_up
-  // (acc_r exact in int32); one wave per row, lane l < LD / 16 (48, or all 64) its 16-B piece (chunk l / 8, k-half (l / 4) % 2,
-  // lane group l % 4) of the row and of the query fragment, sdot4 products, a 64-lane xor tree
+  // (acc_r exact in int32); one wave per row, lane l < LD / 16 (24, 48, or all 64) its 16-B piece
+  // (chunk l / 8, k-half (l / 4) % 2, lane group l % 4) of the row and of the query fragment, sdot4
+  // products, a 64-lane xor tree
   if (novf > 0 && Xh == nullptr) {
     const float4 qs4 = qsc[qi];
     const float qb = qbase[qi];   // base_q
